@@ -34,7 +34,13 @@ question has planted "paraphrase" rows near its embedding in 3-5 target document
 returns real documents and prompts have realistic length (~1k tokens).  Every rank runs TP=1 by
 default (DP replicas; "scaling": weak -- per-GPU load fixed).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--dump-outputs DIR``
+then also writes what the last timed step returned to its caller (rank 0's ``RAGResult`` list) as
+``DIR/<name>.npy``; the corpus, the questions and the date in the prompts are fixed by the arguments,
+so two builds can be compared output for output.  ``--full`` adds what is reported next to the
+headline: the two fast JSON generations per query (``fast_steps_s`` / ``full_pipeline_*``).
 
 With N > 1 and no torch.distributed.run around it, bench.py starts the N ranks itself
 (``parallel/launch.py``: torch.distributed.run as a child process, rendezvous on 127.0.0.1) and
@@ -45,6 +51,7 @@ GPU (RCCL needs one device per rank).
 from __future__ import annotations
 
 import argparse
+import datetime
 import json
 import os
 import sys
@@ -63,6 +70,9 @@ METRIC = "RAG queries/sec + p50 end-to-end latency, bge-base + Llama-3-8B, 1/2/4
 # reference algorithm (benchmarks/reference_rerun.py, profiles/reference_rerun.md): 0.277 q/s per
 # gunicorn worker on one MI355X, x2 for its default of 2 workers (upper bound) -> per GPU.
 BASELINE_QPS_PER_GPU = 0.554
+# The FinalPrompt carries the current date; a fixed one keeps the prompts (the generator's inputs)
+# identical from run to run.
+PROMPT_NOW = datetime.datetime(2024, 1, 1, 12, 0, 0)
 METRIC_CONFIG5 = "RAG queries/sec + p50 end-to-end latency at fixed QPS, bge-large + Llama-3-70B TP=8 (config 5)"
 
 _WORDS = ("account access admin answer api archive backup billing bot calendar campaign channel client cloud "
@@ -222,6 +232,43 @@ def _dump_host_profile(prof):
         f.write(buf.getvalue())
 
 
+def dump_outputs(out_dir: str, results, max_new_tokens: int) -> None:
+    """What the timed path returned in its last step, as float arrays (one row per question, in
+    question order): the answer text as Unicode code points (fixed width, -1 padded, true length in
+    ``answer_len``), the ids of the documents used, the token usage and the retrieval scores kept in
+    the debug info.  A few MB at the default sizes."""
+    def pad(rows, width):
+        a = np.full((len(rows), width), -1.0, dtype=np.float64)
+        for i, r in enumerate(rows):
+            r = list(r)[:width]
+            a[i, :len(r)] = r
+        return a
+
+    def pairs(items):  # "[<id> <score>] ..." -> ids, scores
+        p = [x[1:x.index("]")].split() for x in items]
+        return [float(a) for a, _ in p], [float(b) for _, b in p]
+
+    os.makedirs(out_dir, exist_ok=True)
+    width = 16 * max_new_tokens
+    rel = [pairs(r.debug_info.get("related_questions", [])) for r in results]
+    doc = [pairs(r.debug_info.get("documents", [])) for r in results]
+    n_rel = max([len(a) for a, _ in rel] + [1])
+    n_doc = max([len(a) for a, _ in doc] + [len(r.documents) for r in results] + [1])
+    arrays = {
+        "answer_codepoints": pad([[ord(c) for c in r.answer] for r in results], width).astype(np.float32),
+        "answer_len": np.array([len(r.answer) for r in results], dtype=np.float64),
+        "documents": pad([r.documents for r in results], n_doc),
+        "usage": np.array([[r.usage["prompt_tokens"], r.usage["completion_tokens"]] for r in results],
+                          dtype=np.float64).reshape(len(results), 2),
+        "related_question_ids": pad([a for a, _ in rel], n_rel),
+        "related_question_scores": pad([b for _, b in rel], n_rel),
+        "retrieved_document_ids": pad([a for a, _ in doc], n_doc),
+        "retrieved_document_scores": pad([b for _, b in doc], n_doc),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class _Heartbeat:
     """Rank 0 writes '[bench] <phase> <elapsed>' to stderr when a phase starts and every 60 s
     after, so a long setup (a 70B TP rehearsal builds 8 ranks' shards on one card) is visibly alive;
@@ -289,8 +336,13 @@ def main():
     ap.add_argument("--kv-gb", type=float, default=None)
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--tp", type=int, default=1, help="tensor-parallel size (groups of consecutive ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what is reported next to the headline: the classify / "
+                         "known-question generations (batch mode)")
     ap.add_argument("--no-fast-steps", action="store_true",
-                    help="skip the separately reported classify / known-question generations")
+                    help="with --full: skip the separately reported classify / known-question generations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy")
     ap.add_argument("--config", type=int, choices=(4, 5), default=4,
                     help="BASELINE config: 4 = bge-base + Llama-3-8B, TP=1 per GPU, batch mode (the headline); "
                          "5 = bge-large + Llama-3-70B, TP = --gpus, serve mode at a fixed QPS (--qps, default 4)")
@@ -395,8 +447,14 @@ def main():
             plant_ids.append(rows)
             plant_vecs.append((q_emb[qi] + beta * q_own[qi])[None] + noise)
             plant_docs.append(np.full(len(rows), d, dtype=np.int64))
-    index.add(np.concatenate(plant_ids), torch.cat(plant_vecs), doc_ids=np.concatenate(plant_docs),
-              groups=np.zeros(sum(len(x) for x in plant_ids), dtype=np.int32))
+    # Two questions may draw the same target document: one upsert with a row id twice leaves it to
+    # the device scatter which vector the row ends with, and the index would differ from run to run.
+    # The later question's vector is kept, as upserting them one after the other would.
+    plant_ids, plant_docs = np.concatenate(plant_ids), np.concatenate(plant_docs)
+    _, first_rev = np.unique(plant_ids[::-1], return_index=True)
+    keep = np.sort(len(plant_ids) - 1 - first_rev)
+    index.add(plant_ids[keep], torch.cat(plant_vecs)[torch.from_numpy(keep).to(dev)], doc_ids=plant_docs[keep],
+              groups=np.zeros(len(keep), dtype=np.int32))
     del q_emb, q_own
     rag_lock = threading.Lock() if overlap else None
     rag = RAGPipeline(embedder, index, llm, docs, system_text=SYSTEM_TEXT, retrieve_lock=rag_lock)
@@ -418,6 +476,7 @@ def main():
         return dict(llm.stats), time.perf_counter()
 
     latencies, prompt_lens, n_docs_used = [], [], []
+    last_results = []  # what the last timed step returned (serve: the last B answers completed)
     phases = {"retrieve_s": [], "prompt_s": [], "generate_s": []}
     my_q = all_q[rep]
     if serve:
@@ -436,20 +495,21 @@ def main():
                 if args.tp > 1:  # the TP group's engines must admit the same requests at the same step
                     due = pdist.broadcast_int(due, tp_group, dev)
                 if due > next_q:
-                    rids = rag.submit(my_q[next_q:due], params, bot_group=0)
+                    rids = rag.submit(my_q[next_q:due], params, bot_group=0, now=PROMPT_NOW)
                     for j, rid in enumerate(rids):
                         arrival_of[rid] = t_open + (next_q + j) / args.qps
                     admitted += due - next_q
                     next_q = due
             while (args.qps <= 0 and rag.in_flight + G <= B and next_q + G <= len(my_q)
                    and (admitted >= B or llm.stats["decode_steps"] >= next_admit)):
-                rag.submit(my_q[next_q:next_q + G], params, bot_group=0)
+                rag.submit(my_q[next_q:next_q + G], params, bot_group=0, now=PROMPT_NOW)
                 next_q += G
                 admitted += G
                 next_admit += pace
             for rid, r in rag.poll():
                 done += 1
                 if t0 is not None:
+                    last_results = (last_results + [r])[-B:]
                     sched = arrival_of.pop(rid, None)
                     latencies.append(time.perf_counter() - sched if sched is not None else r.latency_s)
                     prompt_lens.append(r.usage["prompt_tokens"])
@@ -467,7 +527,7 @@ def main():
         # starts once engine 0's first timed batch is decoding, so their phases interleave
         pipes = (rag, rag2)
         for step in range(args.warmup):
-            pipes[step % 2].answer(my_q[step * B:(step + 1) * B], params, bot_group=0)
+            pipes[step % 2].answer(my_q[step * B:(step + 1) * B], params, bot_group=0, now=PROMPT_NOW)
         stats0, t0 = sync_start()
         go = threading.Event()
         results = ([], [])
@@ -486,7 +546,7 @@ def main():
                 with torch.cuda.stream(torch.cuda.Stream(dev)) if gpu else contextlib.nullcontext():
                     for step in range(args.warmup + w, n_steps, 2):
                         qs = my_q[step * B:(step + 1) * B]
-                        rids = pipe.submit(qs, params, bot_group=0)
+                        rids = pipe.submit(qs, params, bot_group=0, now=PROMPT_NOW)
                         pending, got = set(rids), {}
                         while pending:
                             for rid, r in pipe.poll():
@@ -510,6 +570,7 @@ def main():
             t.join()
         if errors:
             raise errors[0]
+        last_results = results[(args.steps - 1) % 2][-1]
         for res in results[0] + results[1]:
             latencies += [r.latency_s for r in res]
             prompt_lens += [r.usage["prompt_tokens"] for r in res]
@@ -522,7 +583,8 @@ def main():
             if step == args.warmup:
                 stats0, t0 = sync_start()
             prof = _host_profiler() if step == args.warmup else None
-            res = rag.answer(my_q[step * B:(step + 1) * B], params, bot_group=0)
+            res = rag.answer(my_q[step * B:(step + 1) * B], params, bot_group=0, now=PROMPT_NOW)
+            last_results = res
             if prof is not None:
                 _dump_host_profile(prof)
             if step >= args.warmup:
@@ -541,10 +603,12 @@ def main():
     # engine counters of the timed region only (before the separately reported fast steps run)
     eng = {k: round(v - stats0.get(k, 0), 3) if isinstance(v, float) else v - stats0.get(k, 0)
            for k, v in llm.stats.items()}
-    # ---- reported separately: the two fast JSON generations per query, after the
-    # timed region so the headline is unchanged
+    if args.dump_outputs and R == 0:
+        dump_outputs(args.dump_outputs, last_results, args.max_new_tokens)
+    # ---- reported separately (--full only): the two fast JSON generations per query,
+    # after the timed region so the headline is unchanged
     fast = None
-    if not args.no_fast_steps and not serve and not overlap:
+    if args.full and not args.no_fast_steps and not serve and not overlap:
         fast = measure_fast_steps(rag, llm, my_q[:B], info, dev)
     p50 = float(np.median(latencies)) if latencies else float("nan")
     p50 = pdist.max_over_ranks(p50, dev)

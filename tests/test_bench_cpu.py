@@ -1,12 +1,15 @@
 """The bench.py driver contract on CPU: one rank and two gloo ranks (the multi-GPU launch shape of
 ``torch.distributed.run``) on the tiny model presets print exactly one JSON line with the required
-keys, the whole-job aggregate and the data-parallel config."""
+keys, the whole-job aggregate and the data-parallel config.  ``--full`` adds the fast JSON steps
+next to the headline; a plain run leaves them out and ``--dump-outputs`` writes what its last timed
+step returned."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +17,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "vs_baseline", "dtype", "data", "config"}
 TINY = ["--embed-model", "tiny-bert", "--llm-model", "tiny-llama", "--index-rows", "5000", "--batch", "4",
         "--max-new-tokens", "6", "--steps", "1", "--warmup", "1"]
+FULL = TINY + ["--full"]  # what _check asserts beyond the headline is measured under --full only
 
 
 def _free_port():
@@ -49,19 +53,19 @@ def _check(d, n):
 
 
 def test_bench_single_rank():
-    _check(_run([sys.executable, "bench.py"] + TINY), 1)
+    _check(_run([sys.executable, "bench.py"] + FULL), 1)
 
 
 def test_bench_two_gloo_ranks():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + TINY
+           "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + FULL
     _check(_run(cmd), 2)
 
 
 def test_bench_self_launches_its_ranks():
     """``python bench.py --gpus 2`` as ONE plain command (the driver's form): the script starts the
     two ranks itself and the JSON reports the world that formed, its backend and per-rank rates."""
-    d = _run([sys.executable, "bench.py", "--gpus", "2"] + TINY)
+    d = _run([sys.executable, "bench.py", "--gpus", "2"] + FULL)
     _check(d, 2)
     assert d["backend"] == "gloo" and len(d["config"]["per_rank_qps"]) == 2
 
@@ -95,3 +99,23 @@ def test_bench_overlap_mode_single_process():
     d = _run([sys.executable, "bench.py", "--gpus", "1", "--mode", "overlap", *args])
     assert d["steps"] == 2 and d["value"] > 0 and d["config"]["mode"].startswith("overlap")
     assert d["value"] == pytest.approx(8 / (2 * d["ms_per_step"] / 1000.0), rel=0.02)
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run reports the headline only (no fast JSON steps), and ``--dump-outputs`` writes the
+    last timed step's answers as float arrays: the same arguments give the same inputs, so on the
+    CPU path (seeded sampling, no atomics) two runs agree array for array."""
+    runs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / name)] + TINY)
+        assert REQUIRED <= set(d) and d["steps"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert not any(k.startswith(("fast_steps", "full_pipeline")) for k in d)
+        assert "fast_steps" not in d["config"]
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert {"answer_codepoints", "answer_len", "documents", "usage"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype in (np.float32, np.float64) and v.shape[0] == 4 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) < 64 * 2 ** 20
+    assert (a["usage"][:, 1] == 6).all() and (a["answer_len"] > 0).all() and (a["documents"][:, 0] >= 0).all()
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,25 @@ def test_bench_modes_on_gpu(mode):
     d = _run([sys.executable, "bench.py", "--mode", mode, *args])
     assert d["config"]["mode"].startswith(mode) and d["config"]["graphs"] is True
     assert d["n_gpus"] == 1
+
+
+def test_bench_dump_outputs_on_gpu(tmp_path):
+    """A plain run on the native path reports the headline only, and ``--dump-outputs`` writes the
+    last timed batch (8 questions) as float arrays.  The arguments fix the inputs (index rows,
+    questions, the date in the prompts) and the kernels reduce in a fixed order, so two runs agree
+    array for array."""
+    runs = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / name), *TINY])
+        assert "fast_steps_s" not in d and "fast_steps" not in d["config"]
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert {"answer_codepoints", "answer_len", "documents", "usage"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype in (np.float32, np.float64) and v.shape[0] == 8 for v in a.values())
+    assert (a["usage"][:, 1] == 8).all() and (a["answer_len"] > 0).all() and (a["documents"][:, 0] >= 0).all()
+    assert ((a["answer_codepoints"] >= 0).sum(1) == np.minimum(a["answer_len"], a["answer_codepoints"].shape[1])).all()
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
 @pytest.mark.parametrize("tp", [1, 2])

@@ -410,7 +410,9 @@ def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, ro
         expect(bias.numel() == N, "bias size mismatch")
     n_out = N // 2 if epilogue in (EPI_SWIGLU, EPI_SWIGLU8) else N
     if epilogue == EPI_SWIGLU:
-        expect(N % 32 == 0 and not out_f32, "swiglu epilogue needs N % 32 == 0 and bf16 output")
+        # (no kernel adds a residual after SwiGLU: gemm.hip's epilogue would store without it)
+        expect(N % 32 == 0 and not out_f32 and residual is None,
+               "swiglu epilogue needs N % 32 == 0, bf16 output, no residual")
     if epilogue == EPI_SWIGLU8:
         expect(N % 32 == 0 and not out_f32 and bias is None and residual is None,
                "swiglu8 epilogue needs N % 32 == 0, bf16 output, no bias / residual")

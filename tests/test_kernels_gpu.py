@@ -347,14 +347,17 @@ def test_gemm_mid(M, N, K):
         assert int(cnt.abs().sum()) == 0
 
 
+@pytest.mark.parametrize("variant", [32, 64])
 @pytest.mark.parametrize("M,N,K", [(300, 512, 256), (1000, 1024, 4096)])
-def test_gemm_mid_k64_variant(M, N, K):
-    """The 64-deep K-step ring (3 stages) of gemm_mid, kept as an A/B arm: same numerics contract."""
+def test_gemm_mid_k_step_variants(M, N, K, variant):
+    """The forced K-steps of gemm_mid: 64 (the 3-stage ring, which is also the default) and 32 (the
+    6-stage ring kept as an A/B arm): same numerics contract."""
     A, B = bf(M, K), bf(N, K, scale=0.05)
     Bs = ops.shuffle_weights(B)
-    close(ops.kernels.gemm_mid(A, Bs, variant=64), ref.gemm_bt(A, B), atol=3e-2, rtol=2e-2)
+    close(ops.kernels.gemm_mid(A, Bs, variant=variant), ref.gemm_bt(A, B), atol=3e-2, rtol=2e-2)
     res = bf(M, N)
-    close(ops.kernels.gemm_mid(A, Bs, residual=res, variant=64), ref.gemm_bt(A, B, None, res), atol=3e-2, rtol=2e-2)
+    close(ops.kernels.gemm_mid(A, Bs, residual=res, variant=variant), ref.gemm_bt(A, B, None, res), atol=3e-2,
+          rtol=2e-2)
 
 
 def test_gemm_mid_in_a_strided_view_and_out_buffer():
@@ -487,7 +490,7 @@ def test_gemm_swiglu():
 
 
 @pytest.mark.parametrize("cfg,M,N,K,S", _stream_cases(
-    list(range(17)) + [20, 21, 22, 23, 25, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37],
+    list(range(17)) + [20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37],
     [1, 16, 30, 37, 64, 100, 128, 200, 256],
     [(256, 512, 1), (384, 1024, 4), (128, 1792, 7), (256, 4096, 16), (512, 1280, 1), (672, 512, 1),
      (1344, 1024, 4), (2688, 1792, 7)]))

@@ -196,13 +196,13 @@ PYBIND11_MODULE(_native, m) {
     return r;
   });
   m.def("gemm256", [](u A, long lda, u B, long ldb, u C, long ldc, u bias, u residual, long ldr, int M, int N, int K,
-                      int epilogue, u s, int b_shuf, int b_group) {
+                      int epilogue, u s, int b_shuf, int b_group, u rows, int src_rows) {
     check(dab::gemm256(CVP(A), lda, CVP(B), ldb, VP(C), ldc, CVP(bias), CVP(residual), ldr, M, N, K, epilogue, ST(s),
-                       b_shuf, b_group),
+                       b_shuf, b_group, reinterpret_cast<const int*>(rows), src_rows),
           "gemm256");
   }, py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("ldb"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
      py::arg("residual"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epilogue"), py::arg("s"),
-     py::arg("b_shuf") = 0, py::arg("b_group") = 1);
+     py::arg("b_shuf") = 0, py::arg("b_group") = 1, py::arg("rows") = 0, py::arg("src_rows") = 0);
   m.def("gemm_score_candidates", [](u A, long lda, u B, long ldb, int M, int N, int K, u row_group, u q_group, u thr,
                                     u cnt, u cand_val, u cand_idx, int cap, u s) {
     check(dab::gemm_score_candidates(CVP(A), lda, CVP(B), ldb, M, N, K, reinterpret_cast<const int*>(row_group),

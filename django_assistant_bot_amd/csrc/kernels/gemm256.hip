@@ -72,6 +72,10 @@ struct G256 {
   // of the epilogue} as one 16-B vector store; stamp_tiles entries per workgroup
   u32x4* stamps;
   int stamp_tiles;
+  // ROWS (row-subset mode): C[r] = A[rows[r]] . B^T (+ residual[rows[r]]) for r < M, written compact
+  // [M, N]; A and the residual have src_rows rows.  Any order, duplicates allowed.
+  const int* rows;
+  int src_rows;
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -118,6 +122,13 @@ static_assert(2 * kBuf + kCandExtra <= 163840, "LDS");
 
 }  // namespace
 
+// ROWS: byte offset of element 8 c of source row rows[r] (row stride ld), or one past any range the
+// launcher admits (2 GB) for a compact row r >= n
+constexpr unsigned kPastRange = 0x80000000u;
+__device__ __forceinline__ unsigned row_off(const int* rows, int n, long ld, int r, int c) {
+  return r < n ? (unsigned)(((long)rows[r] * ld + 8 * c) * 2) : kPastRange;
+}
+
 // grouped tile order: tile id -> (m0, n0), column-major inside groups of GM tile rows
 __device__ __forceinline__ void tile_of(int sid, int tiles_m, int tiles_n, int GM, int& m0, int& n0) {
   const int per_group = GM * tiles_n;
@@ -128,7 +139,7 @@ __device__ __forceinline__ void tile_of(int sid, int tiles_m, int tiles_n, int G
   n0 = (inner / gsz) << 8;
 }
 
-template <int EPI, bool BIAS, bool RES, bool SHUF = false, bool STAMP = false, int SAUX = 0>
+template <int EPI, bool BIAS, bool RES, bool SHUF = false, bool STAMP = false, int SAUX = 0, bool ROWS = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kBuf + (EPI == G_CAND ? kCandExtra : 0)];
   // stores per wave in the epilogue (the next tile's first waits count past them; the candidate
@@ -219,8 +230,16 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   const int srow = 8 * w + (lane >> 3);
   // whole row offsets in VOFFSET (the buffer range check sees them: rows >= M / N read zeros);
   // the K offset goes in SOFFSET
-  const unsigned vA0 = (unsigned)((srow * p.lda + 8 * cc) * 2), vA1 = vA0 + (unsigned)(64 * p.lda * 2);
-  const unsigned vA2 = vA0 + (unsigned)(128 * p.lda * 2), vA3 = vA0 + (unsigned)(192 * p.lda * 2);
+  unsigned vA0 = (unsigned)((srow * p.lda + 8 * cc) * 2), vA1 = vA0 + (unsigned)(64 * p.lda * 2);
+  unsigned vA2 = vA0 + (unsigned)(128 * p.lda * 2), vA3 = vA0 + (unsigned)(192 * p.lda * 2);
+  // ROWS: piece j of the tile at compact row mm reads source row rows[mm + srow + 64 j].  The whole
+  // A is one descriptor range (< 2 GB, checked by the launcher) and a compact row >= M gets an offset
+  // past it, so it still reads zeros.  A lane's four row ids are loaded once per tile: here for the
+  // first, and for every later tile where the K-loop turns to it (phase 1 of the last iteration).
+  if constexpr (ROWS) {
+    vA0 = row_off(p.rows, p.M, p.lda, m0 + srow, cc), vA1 = row_off(p.rows, p.M, p.lda, m0 + srow + 64, cc);
+    vA2 = row_off(p.rows, p.M, p.lda, m0 + srow + 128, cc), vA3 = row_off(p.rows, p.M, p.lda, m0 + srow + 192, cc);
+  }
   // SHUF: wave w copies 16-row block w of each 128-row half, both 32-k blocks of the K-tile
   // (1 KB each, lane-linear); block (rb, kb) of a K-tile sits at byte (K / 32 rb + kb) 1 KB
   const unsigned kblk = (unsigned)(p.K / 32) * 1024u;
@@ -234,6 +253,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   const unsigned vB2 = SHUF ? vB0 + 8u * kblk : vB0 + (unsigned)(128 * p.ldb * 2);
   const unsigned vB3 = SHUF ? vB2 + cb : vB0 + (unsigned)(192 * p.ldb * 2);
   auto rsrc_a = [&](int mm) {
+    if constexpr (ROWS) return make_rsrc(p.A, (unsigned)(((long)(p.src_rows - 1) * p.lda + p.K) * 2));
     const long rows = min(256, p.M - mm);
     return make_rsrc(p.A + (size_t)mm * p.lda, (unsigned)(((rows - 1) * p.lda + p.K) * 2));
   };
@@ -366,6 +386,17 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
       G256_READ_B(0, 0)
       G256_READ_B(0, 1)
       stage(1, 1, o, rA, rB);
+      if constexpr (ROWS) {
+        // that was this tile's last A piece: phases 2-4 stage the next tile's first K-tiles, so its
+        // row ids replace this tile's.  The asm needs the values, which puts the wait for them here:
+        // one drain of the VM queue per tile, after which the counted waits below only cover loads
+        // that have landed.  A row-subset launch has few tiles (ceil(M / 256) N / 256).
+        if (last && more) {
+          vA0 = row_off(p.rows, p.M, p.lda, nm0 + srow, cc), vA1 = row_off(p.rows, p.M, p.lda, nm0 + srow + 64, cc);
+          vA2 = row_off(p.rows, p.M, p.lda, nm0 + srow + 128, cc), vA3 = row_off(p.rows, p.M, p.lda, nm0 + srow + 192, cc);
+          asm volatile("" : "+v"(vA0), "+v"(vA1), "+v"(vA2), "+v"(vA3));
+        }
+      }
       if (fe) wait_vm<8 + kEpi>();
       else wait_vm<8>();
       read_bar();
@@ -618,7 +649,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
       }
       __amdgpu_buffer_rsrc_t rR = rC;
       if constexpr (RES) {
-        rR = make_rsrc(p.residual + (size_t)m0 * p.ldr, (unsigned)(c_rows * p.ldr * 2));
+        // ROWS: the residual is gathered by the same row ids (one descriptor over all of it)
+        if constexpr (ROWS) rR = make_rsrc(p.residual, (unsigned)(((long)(p.src_rows - 1) * p.ldr + p.N) * 2));
+        else rR = make_rsrc(p.residual + (size_t)m0 * p.ldr, (unsigned)(c_rows * p.ldr * 2));
       }
       // RES: all 16 residual vectors of the wave are requested before the first store (64 VGPRs,
       // the dead fragment registers), so one vmcnt(0) per tile instead of one per 128-row half
@@ -631,12 +664,21 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
 #pragma unroll
         for (int ih = 0; ih < 2; ++ih)
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
+          for (int i = 0; i < 4; ++i) {
+            if constexpr (ROWS) {
+              const unsigned ro = row_off(p.rows, p.M, p.ldr, m0 + 128 * ih + 64 * wr + 16 * i + e_li, 0);
+#pragma unroll
+              for (int jh = 0; jh < 2; ++jh)
+                rvv[ih][i][jh] = __builtin_amdgcn_raw_buffer_load_b128(
+                    rR, ro + (unsigned)((n0 + 128 * jh + 32 * e_wc + cq) * 2), 0, 0);
+              continue;
+            }
 #pragma unroll
             for (int jh = 0; jh < 2; ++jh)
               rvv[ih][i][jh] = __builtin_amdgcn_raw_buffer_load_b128(
                   rR, (unsigned)(((128 * ih + 64 * wr + 16 * i + e_li) * p.ldr + n0 + 128 * jh + 32 * e_wc + cq) * 2), 0,
                   0);
+          }
       }
 #pragma unroll
       for (int ih = 0; ih < 2; ++ih) {
@@ -842,10 +884,21 @@ int gemm256_ok(int M, int N, int K, long lda, long ldb) {
 
 // b_shuf: B is in the shuffle_weights layout (ldb == K).  Epilogues: 0 none, 1 GELU, 2 SwiGLU over
 // 16-row [gate | up] groups, 4 SwiGLU over 8-row groups (no bias); bias / residual optional.
+// rows (row-subset mode): int32 [M] device row ids into A and the residual, which have src_rows
+// rows; C is compact [M, N] and every computed element goes through the arithmetic of the plain
+// call (the accumulation order of an element depends neither on M nor on its place in a tile).
+// Epilogues 0 (+ residual) and 4, no bias.
 int gemm256(const void* A, long lda, const void* B, long ldb, void* C, long ldc, const void* bias,
             const void* residual, long ldr, int M, int N, int K, int epilogue, hipStream_t s, int b_shuf,
-            int b_group) {
+            int b_group, const int* rows, int src_rows) {
   if (!gemm256_ok(M, N, K, lda, ldb)) return hipErrorInvalidValue;
+  if (rows) {
+    // one descriptor spans all of A (and of the residual): offsets below 2 GB, so that a row past
+    // the list can be given one outside the range
+    if (src_rows <= 0 || bias || (epilogue != G_NONE && epilogue != G_SWIGLU8)) return hipErrorInvalidValue;
+    if (((long)(src_rows - 1) * lda + K) * 2 >= (1L << 31)) return hipErrorInvalidValue;
+    if (residual && ((long)(src_rows - 1) * ldr + N) * 2 >= (1L << 31)) return hipErrorInvalidValue;
+  }
   if (b_group != 1 && !(b_group == 8 && b_shuf)) return hipErrorInvalidValue;  // (N % 256: whole groups)
   if ((epilogue == G_SWIGLU || epilogue == G_SWIGLU8) && residual) return hipErrorInvalidValue;
   if (epilogue == G_SWIGLU8 && bias) return hipErrorInvalidValue;
@@ -865,6 +918,8 @@ int gemm256(const void* A, long lda, const void* B, long ldb, void* C, long ldc,
   p.ldr = ldr;
   p.rows_b = N;
   p.bgrp = b_group;
+  p.rows = rows;
+  p.src_rows = src_rows;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const int tiles = ((M + 255) / 256) * (N / 256);
@@ -872,6 +927,18 @@ int gemm256(const void* A, long lda, const void* B, long ldb, void* C, long ldc,
   // persistent: one workgroup (128 KB of LDS) per CU walks a strided tile list
   const int nwg = tiles > cus ? cus : tiles;
   const bool hb = bias != nullptr, hr = residual != nullptr;
+  if (rows) {
+#define G256_LAUNCH_ROWS(E, R)                                                                                       \
+  do {                                                                                                               \
+    if (b_shuf) hipLaunchKernelGGL((gemm256_kernel<E, false, R, true, false, 0, true>), dim3(nwg), dim3(512), 0, s, p); \
+    else hipLaunchKernelGGL((gemm256_kernel<E, false, R, false, false, 0, true>), dim3(nwg), dim3(512), 0, s, p);    \
+  } while (0)
+    if (epilogue == G_SWIGLU8) G256_LAUNCH_ROWS(G_SWIGLU8, false);
+    else if (hr) G256_LAUNCH_ROWS(G_NONE, true);
+    else G256_LAUNCH_ROWS(G_NONE, false);
+#undef G256_LAUNCH_ROWS
+    return hipGetLastError();
+  }
 #define G256_LAUNCH_AUX(E, B, R, AX)                                                                          \
   do {                                                                                                         \
     if (b_shuf) hipLaunchKernelGGL((gemm256_kernel<E, B, R, true, false, AX>), dim3(nwg), dim3(512), 0, s, p); \

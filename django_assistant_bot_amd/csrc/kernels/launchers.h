@@ -68,7 +68,8 @@ int gemm256_candidates(const void* A, long lda, const void* B, long ldb, int M, 
                        const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx, int cap,
                        hipStream_t s, int b_rows = 0);
 // b_shuf: B in the ops.shuffle_weights layout (the decode GEMM's copy); epilogue 4 = SwiGLU over
-// 8-row [gate | up] groups
+// 8-row [gate | up] groups; rows: C[r] = A[rows[r]] . B^T (+ residual[rows[r]]), compact [M, N], A and
+// the residual of src_rows rows (epilogues 0 and 4, no bias)
 // diagnostic per-tile s_memtime stamps (benchmarks/gemm_stamps.py); returns the grid or -error
 int gemm256_candidates_stamped(const void* A, long lda, const void* B, int M, int N, int K, int b_rows,
                                const float* thr, int* cnt, float* cand_val, int* cand_idx, int cap, void* stamps,
@@ -77,7 +78,7 @@ int gemm256_stamped(const void* A, long lda, const void* B, void* C, const void*
                     int N, int K, int epilogue, int b_shuf, void* stamps, int stamp_tiles, hipStream_t s, int store_aux);
 int gemm256(const void* A, long lda, const void* B, long ldb, void* C, long ldc, const void* bias,
             const void* residual, long ldr, int M, int N, int K, int epilogue, hipStream_t s, int b_shuf = 0,
-            int b_group = 1);
+            int b_group = 1, const int* rows = nullptr, int src_rows = 0);
 
 // gemm_mid.hip (M = 256..4096: mixed serving steps / single prompts; grouped stream-K over the N x K
 // plane, 128 x 256 tiles, in-launch last-arriver combine; B in the shuffle_weights layout;

@@ -475,15 +475,20 @@ class LLMEngine:
         to = self._h2d
         meta = AttnMeta(decode=False, positions=to(pos), slots=to(slots), block_tables=to(bt), ctx_lens=to(ctx),
                         cu_q=to(cu), max_q=max(n for _, _, n in chunks))
-        with self.timer.phase("prefill"):
-            hidden = self.model.forward(to(ids), meta, self.kv)
+        # only the last row of each prompt that ends here is read: the model runs the last layer's
+        # row-wise tail on those rows alone where it can (``LlamaModel.forward`` ``out_rows``)
         last_rows = [i for i, (r, s, n) in enumerate(chunks) if s + n == len(r.full_prompt())]
+        if last_rows:
+            sel = self._h2d(torch.as_tensor([int(cu[i + 1]) - 1 for i in last_rows], dtype=torch.int32))
+        else:
+            sel = torch.empty(0, dtype=torch.int32, device=self.device)
+        with self.timer.phase("prefill"):
+            hidden = self.model.forward(to(ids), meta, self.kv, out_rows=sel)
         self.stats["prefill_tokens"] += T
         self.stats["prefill_steps"] += 1
         reqs, toks = [], []
         if last_rows:
-            sel = self._h2d(torch.as_tensor([int(cu[i + 1]) - 1 for i in last_rows], dtype=torch.long))
-            logits = self.model.logits(hidden.index_select(0, sel))
+            logits = self.model.logits(hidden)
             reqs = [chunks[i][0] for i in last_rows]
             toks = self._sample(logits, reqs, to_host=not self.is_gpu)
         for r, s, n in chunks:
@@ -579,12 +584,12 @@ class LLMEngine:
                         cu_q=to(cu), max_q=max(n for _, _, n in chunks), workspace=self._workspace,
                         part_size=self._decode_part(Bp), n_decode=Bp, dec_block_tables=self._d_bt[:Bp],
                         dec_ctx_lens=self._d_ctx[:Bp], order=order)
-        with self.timer.phase("mixed"):
-            hidden = self.model.forward(to(ids), meta, self.kv)
         last_rows = [i for i, (r, s, n) in enumerate(chunks) if s + n == len(r.full_prompt())]
         sel = [int(cu[i + 1]) - 1 for i in last_rows] + list(range(Tp, Tp + B))
-        sel_d = torch.as_tensor(sel, dtype=torch.long).to(dev, non_blocking=True)
-        logits = self.model.logits(hidden.index_select(0, sel_d))
+        sel_d = torch.as_tensor(sel, dtype=torch.int32).to(dev, non_blocking=True)
+        with self.timer.phase("mixed"):
+            hidden = self.model.forward(to(ids), meta, self.kv, out_rows=sel_d)
+        logits = self.model.logits(hidden)
         preqs = [chunks[i][0] for i in last_rows]
         self._tp_fault_enqueue()
         toks = self._sample(logits, preqs + batch)

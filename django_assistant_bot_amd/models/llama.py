@@ -332,8 +332,30 @@ class LlamaModel:
                 return ops.slab_reduce(out) if (s > 1 and not allow_slabs) else out
         return ops.gemm_bt(x, w, epilogue=epilogue, shuffled=self.frag, b_group=grp)
 
-    def forward(self, ids: torch.Tensor, meta: AttnMeta, kv: KVCache) -> torch.Tensor:
-        """ids int32 [T] -> final hidden states [T, H] (after the last RMSNorm)."""
+    # Pure prefill steps whose caller reads only ``out_rows`` (the last token of each finished
+    # prompt, ~30 rows of 32k): everything after the LAST layer's attention is row-wise -- o + residual,
+    # MLP norm, gate_up + SwiGLU, down + residual, final norm -- so it runs on those rows alone (one
+    # layer's o / gate_up / down GEMMs and two norm passes less per step).  The rows go through the
+    # kernels the full step would have taken (gemm256 ``rows`` / ``as_m``: an element's arithmetic
+    # depends neither on M nor on its tile row), so the result is bit-identical; steps whose full
+    # call takes another kernel (mid-M, streamed, TP, CPU, mixed) run whole and select afterwards.
+    # Switch for the A/B and the equality tests.
+    prune_last_tail = True
+
+    def _tail_prunable(self, T: int, meta: AttnMeta, x: torch.Tensor, sk: bool) -> bool:
+        if not (self.prune_last_tail and x.is_cuda and not sk and not meta.decode and not meta.n_decode
+                and self.tp_size == 1 and self.frag and T >= ops.kernels.GEMM256_MIN_M):
+            return False
+        L = self.layers[-1]
+        for N, K in (L.o_w.shape, L.gate_up_w.shape, L.down_w.shape):  # (contiguous activations: lda = K)
+            if ops.kernels.use_gemm_mid(T, N, K, K) or not ops.kernels.use_gemm256(T, N, K, K, K):
+                return False
+        return True
+
+    def forward(self, ids: torch.Tensor, meta: AttnMeta, kv: KVCache,
+                out_rows: torch.Tensor | None = None) -> torch.Tensor:
+        """ids int32 [T] -> final hidden states [T, H] (after the last RMSNorm); with ``out_rows``
+        (int32 / int64 [n] row ids, on the device of ``ids``) only those rows, [n, H]."""
         cfg = self.cfg
         D = cfg.head_dim
         T = ids.numel()
@@ -350,11 +372,17 @@ class LlamaModel:
             h = x  # the residual stream itself: no RMSNorm launches (``_layer_small``)
             for li, L in enumerate(self.layers):
                 h = self._layer_small(li, L, h, meta, kv)
-            return ops.rmsnorm(h, self.final_norm, self.cfg.eps)[0]
+            h = ops.rmsnorm(h, self.final_norm, self.cfg.eps)[0]
+            return h if out_rows is None else h.index_select(0, out_rows)
         residual = None
+        prune = out_rows is not None and self._tail_prunable(T, meta, x, sk)
         for li, L in enumerate(self.layers):
-            x, residual = self._layer(li, L, x, residual, meta, kv, sk)
-        return self._final_norm(x, residual)
+            rows = out_rows if prune and li == len(self.layers) - 1 else None
+            x, residual = self._layer(li, L, x, residual, meta, kv, sk, rows)
+        if prune and out_rows.numel() == 0:  # no prompt ends in this chunk: only the K / V writes were due
+            return residual
+        h = self._final_norm(x, residual)
+        return h if out_rows is None or prune else h.index_select(0, out_rows)
 
     # Small decode batches (the interactive case): the residual stream h is the
     # only activation between layers.  The o / down projections stream their weights without split-K
@@ -432,8 +460,10 @@ class LlamaModel:
             x = ops.slab_reduce(x)
         return self._all_reduce(x)
 
-    def _layer(self, li: int, L: DecoderLayer, x, residual, meta: AttnMeta, kv: KVCache, sk: bool):
-        """One decoder layer: (layer input, residual stream) -> (next layer input, residual stream)."""
+    def _layer(self, li: int, L: DecoderLayer, x, residual, meta: AttnMeta, kv: KVCache, sk: bool, rows=None):
+        """One decoder layer: (layer input, residual stream) -> (next layer input, residual stream).
+        ``rows`` (``forward``'s ``out_rows``, last layer of a prunable step): the part after the
+        attention runs on these rows only and the residual stream returned is compact [n, H]."""
         cfg, D, T = self.cfg, self.cfg.head_dim, meta.positions.numel()  # x may be [S, T, H] split-K slabs
         slabs_ok = self.tp_size == 1  # under TP the partial sums go through the all-reduce as bf16
         # prefill (TP 1): the o / down GEMMs add the residual in their epilogue (gemm256 RES, rounded
@@ -457,6 +487,8 @@ class LlamaModel:
             q = qkv[:, :self.hq * D].view(T, self.hq, D)
             a = ops.flash_attention_paged(q, kv.k[li], kv.v[li], meta.block_tables, meta.cu_q, meta.ctx_lens,
                                           meta.max_q, causal=True, rope=(meta.positions, self.cos_sin))
+            if rows is not None:
+                return self._layer_tail_rows(L, a, residual, rows, T, D)
             return self._layer_tail(L, a, residual, sk, fuse, slabs_ok, T, D)
         q = ops.rope_kv_write(qkv, meta.positions, self.cos_sin, kv.k[li], kv.v[li], meta.slots, self.hq, self.hkv, D)
         if meta.decode:
@@ -467,7 +499,25 @@ class LlamaModel:
         else:
             a = ops.flash_attention_paged(q, kv.k[li], kv.v[li], meta.block_tables, meta.cu_q, meta.ctx_lens,
                                           meta.max_q, causal=True)
+        if rows is not None:
+            return self._layer_tail_rows(L, a, residual, rows, T, D)
         return self._layer_tail(L, a, residual, sk, fuse, slabs_ok, T, D)
+
+    def _layer_tail_rows(self, L, a, residual, rows, T, D):
+        """``_layer_tail`` (its ``fuse`` form) for the rows ``rows`` of a T-token step whose o / gate_up
+        / down run on gemm256 (``_tail_prunable``): the o projection gathers its rows of ``a`` and of
+        the residual stream inside the kernel, the rest runs on the compact rows as a T-row call would."""
+        n = rows.numel()
+        if n == 0:
+            return None, residual.new_empty((0, residual.shape[1]))
+        if rows.dtype != torch.int32:
+            rows = rows.to(torch.int32)
+        pg = self.proj_group
+        res = ops.gemm_bt(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=True, b_group=pg.get("o", 1),
+                          rows=rows)
+        h, _ = ops.rmsnorm(res, L.mlp_norm, self.cfg.eps)
+        act = ops.gemm_bt(h, L.gate_up_w, epilogue=ops.EPI_SWIGLU8, shuffled=True, b_group=pg.get("gate_up", 1), as_m=T)
+        return None, ops.gemm_bt(act, L.down_w, residual=res, shuffled=True, b_group=pg.get("down", 1), as_m=T)
 
     def _layer_tail(self, L, a, residual, sk, fuse, slabs_ok, T, D):
         """o projection, MLP norm, gate_up (+SwiGLU), down: -> (next layer input, residual stream)."""

@@ -381,13 +381,31 @@ def use_gemm256(M: int, N: int, K: int, lda: int, ldb: int) -> bool:
 
 
 def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, row_group=None, q_group=None,
-            allow=None, out=None, shuffled=False, n=None, b_group: int = 1):
+            allow=None, out=None, shuffled=False, n=None, b_group: int = 1, rows=None, as_m=None):
     """C = A . B^T (+bias) (+act) (+residual) on MFMA; A [M, K], B [N, K] (K-contiguous rows).
 
     ``shuffled``: B is a ``shuffle_weights`` copy (the layout the decode GEMM streams, so a model
     keeps ONE copy of every projection) of ``B.shape[0]`` rows, of which the first ``n`` (default:
-    all) are the matrix; ``b_group`` 8: a ``shuffle_weights(w, 8)`` copy."""
+    all) are the matrix; ``b_group`` 8: a ``shuffle_weights(w, 8)`` copy.
+
+    Row subsets, bit-identical to the rows of the full call (the last prefill layer's tail, of which
+    only a few rows are read): ``rows`` (int32 [n], device, any order, duplicates allowed) gives
+    ``gemm_bt(A, B, residual=R)[rows]`` as a compact [n, N] without computing the other rows -- A
+    and the residual are gathered inside the kernel; ``as_m`` makes a call on already compact rows
+    take the kernel that ``as_m`` rows would.  Both hold only where that kernel is gemm256, whose
+    result for an element depends neither on M nor on the row's place in a tile; any other shape
+    is refused."""
     expect(b_group == 1 or (shuffled and b_group == 8), "b_group: 1, or 8 with a shuffled copy")
+    if rows is not None or as_m is not None:
+        expect(out_f32 is False and row_group is None and q_group is None and allow is None and bias is None
+               and n is None and epilogue in (EPI_NONE, EPI_SWIGLU8),
+               "row subsets: plain / residual / SwiGLU8 projections only")
+        expect(rows is None or as_m is None, "row subsets: rows or as_m, not both")
+        if not A.is_cuda:
+            y = gemm_bt(A, B, residual=residual, epilogue=epilogue, shuffled=shuffled, b_group=b_group)
+            y = y if rows is None else y.index_select(0, rows.long())
+            return y if out is None else out.copy_(y)
+        return _gemm256_rows(A, B, residual, epilogue, shuffled, b_group, rows, as_m, out)
     if shuffled:
         R = B.shape[0]
         N = R if n is None else int(n)
@@ -448,17 +466,56 @@ def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, ro
     return out
 
 
-def _gemm256_into(A, B, out, bias, residual, epilogue, shuffled, b_group=1):
+def _gemm256_into(A, B, out, bias, residual, epilogue, shuffled, b_group=1, rows=None):
     M, K = A.shape
     native().gemm256(ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(out), out.stride(0), ptr(bias), ptr(residual),
-                     residual.stride(0) if residual is not None else 0, M, B.shape[0], K, int(epilogue), stream(A),
-                     int(shuffled), int(b_group))
+                     residual.stride(0) if residual is not None else 0, M if rows is None else rows.numel(), B.shape[0],
+                     K, int(epilogue), stream(A), int(shuffled), int(b_group), ptr(rows), M if rows is not None else 0)
     return out
 
 
-def gemm256(A, B, bias=None, residual=None, epilogue=EPI_NONE, shuffled=False, b_group: int = 1):
+def _gemm256_rows(A, B, residual, epilogue, shuffled, b_group, rows, as_m, out=None, direct=False):
+    """``gemm_bt`` with ``rows`` / ``as_m``: the dispatch follows the full row count and must end
+    at gemm256 (``direct``: ``ops.gemm256``, which takes any M)."""
+    expect(A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16, "bf16 operands required")
+    expect(A.dim() == 2 and B.dim() == 2 and A.stride(-1) == 1 and B.stride(-1) == 1 and B.shape[1] == A.shape[1],
+           "operands must be K-contiguous [M, K] / [N, K]")
+    (M, K), N = A.shape, B.shape[0]
+    full = M if rows is not None else int(as_m)
+    n_out = N // 2 if epilogue == EPI_SWIGLU8 else N
+    if rows is not None:
+        _i32(rows)
+        expect(rows.is_cuda and rows.dim() == 1, "rows: int32 [n] on the device")
+    else:
+        expect(full >= M, "as_m: at least the rows of A")
+    expect(epilogue == EPI_NONE or residual is None, "swiglu8 epilogue takes no residual")
+    if residual is not None:
+        expect(residual.dtype == torch.bfloat16 and residual.stride(-1) == 1 and tuple(residual.shape) == (M, n_out),
+               "residual must be bf16 row-major [M, N]")
+    lda = A.stride(0)
+    mid = shuffled and use_gemm_mid(full, N, K, lda)
+    expect(direct or (not mid and use_gemm256(full, N, K, lda, B.stride(0))),
+           "row subsets need the shape's full call on gemm256 (not gemm_mid or the 128 x 128 kernel)")
+    expect(bool(native().gemm256_ok(M, N, K, lda, B.stride(0))), "gemm256: N % 256, K % 128, 16-B rows")
+    expect(not shuffled or (B.is_contiguous() and B.shape[1] == K), "shuffled B must be a contiguous [N, K] copy")
+    n = M if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty((n, n_out), dtype=torch.bfloat16, device=A.device)
+    expect(out.dtype == torch.bfloat16 and out.stride(-1) == 1 and tuple(out.shape) == (n, n_out)
+           and (n <= 1 or out.stride(0) % 8 == 0), "bad output buffer")
+    if n == 0:
+        return out
+    return _gemm256_into(A, B, out, None, residual, epilogue, shuffled, b_group, rows)
+
+
+def gemm256(A, B, bias=None, residual=None, epilogue=EPI_NONE, shuffled=False, b_group: int = 1, rows=None,
+            out=None):
     """The phased 256x256 kernel directly, for any M (``gemm_bt`` takes it from M >= 1024):
-    tests and benchmarks.  N % 256 == 0, K % 128 == 0."""
+    tests and benchmarks.  N % 256 == 0, K % 128 == 0.  ``rows``: the row-subset mode (see
+    ``gemm_bt``), into ``out`` [n, N] if given."""
+    if rows is not None:
+        expect(A.is_cuda and bias is None, "gemm256 rows: CUDA operands, no bias")
+        return _gemm256_rows(A, B, residual, epilogue, shuffled, b_group, rows, None, out, direct=True)
     M, K = A.shape
     N = B.shape[0]
     expect(A.is_cuda and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16, "bf16 CUDA operands required")

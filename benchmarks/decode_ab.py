@@ -96,6 +96,8 @@ ARMS = {
     "gu27": {"gate_up": (27, 1)},  # batches 129..256: gate_up on the M <= 256 streaming tiles (round-6 default: gemm_mid)
     "gu41": {"gate_up": (41, 1)},
     "gu42": {"gate_up": (42, 1)},
+    # the opt-in FP8 KV cache: a second engine on the same model (its own pool, scheduler and graphs)
+    "kvfp8": {"_kv": "fp8"},
 }
 
 
@@ -136,6 +138,11 @@ def main():
     prompts = [torch.randint(0, 128000, (args.prompt + int(torch.randint(-100, 100, (1,), generator=g)),),
                              generator=g).tolist() for _ in range(args.batch)]
 
+    eng16, eng8 = eng, None
+    if any(ARMS[a].get("_kv") == "fp8" for a in args.arms.split(",")):
+        eng8 = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=60, max_prefill_tokens=32768,
+                         block_size=args.block_size, shared_model=eng.model, kv_cache_dtype="fp8")
+
     def restart():
         """Every arm decodes from the same contexts: drop the batch and re-admit the same prompts
         (their blocks come back from the prefix cache, so only the last partial block re-runs)."""
@@ -155,6 +162,7 @@ def main():
     for r in range(args.rounds):
         for a in arms:
             spec = dict(ARMS[a])
+            eng = eng8 if spec.get("_kv") == "fp8" else eng16  # (restart() and the steps below follow it)
             restart()
             eng.model.overrides = {k: v for k, v in spec.items() if not k.startswith("_")}
             eng.long_part_size = spec.get("_part", base_part)

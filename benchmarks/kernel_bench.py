@@ -290,6 +290,53 @@ def decode_sweep():
         del kc, vc
 
 
+def decode_fp8_sweep(rounds=5, iters=30):
+    """Paged decode attention, bf16 cache vs FP8 cache (``ops.paged_decode_fp8``), on the same
+    contexts and block tables: batch 128 at ~1.1-1.4k (one-slot kernels, partitions of 2048 as the
+    engine picks them) and batch 1 / 8 at 1k and 8k (two-slot kernels, partitions of 512).  The two arms
+    alternate round by round (``rounds`` rounds of ``iters`` launches, the median round is reported); TB/s
+    counts the bytes each arm actually reads: 256 per cached row and side for bf16, 129 for FP8."""
+    Hq, Hkv, D, bs = 32, 8, 128, 64
+    g = torch.Generator().manual_seed(0)
+    shapes = [(128, 1100, 1400, 2048), (1, 1024, 1025, 512), (8, 1024, 1025, 512), (1, 8192, 8193, 512),
+              (8, 8192, 8193, 512)]
+    for Bd, lo, hi, part in shapes:
+        ctx_h = torch.randint(lo, hi, (Bd,), generator=g)
+        nbs = [math.ceil(int(c) / bs) for c in ctx_h]
+        nbd = sum(nbs)
+        kc = torch.randn(nbd, Hkv, bs, D, device="cuda").to(torch.bfloat16)
+        vc = torch.randn_like(kc)
+        kd, ke = ops.kv_quantize(kc.cpu())
+        vd, ve = ops.kv_quantize(vc.cpu())
+        kd, ke, vd, ve = (t.contiguous().cuda() for t in (kd, ke, vd, ve))
+        perm = torch.randperm(nbd, generator=g)
+        bt = torch.zeros((Bd, max(nbs)), dtype=torch.int32)
+        o = 0
+        for i, n in enumerate(nbs):
+            bt[i, :n] = perm[o:o + n].to(torch.int32)
+            o += n
+        bt = bt.cuda()
+        qd = torch.randn(Bd, Hq, D, device="cuda").to(torch.bfloat16)
+        ctx = ctx_h.to(torch.int32).cuda()
+        ws = ops.DecodeWorkspace(Bd, Hq, D, math.ceil(max(nbs) * bs / part), "cuda")
+        arms = {"bf16": lambda: ops.paged_decode(qd, kc, vc, bt, ctx, part, ws),
+                "fp8": lambda: ops.paged_decode_fp8(qd, kd, ke, vd, ve, bt, ctx, part, ws)}
+        times = {k: [] for k in arms}
+        for _ in range(rounds):
+            for k, fn in arms.items():
+                times[k].append(timeit(fn, iters=iters))
+        rows = 2.0 * float(ctx_h.sum()) * Hkv
+        res = {"op": "paged-decode-fp8-ab", "B": Bd, "mean_ctx": int(ctx_h.float().mean()), "part": part}
+        for k, per_row in (("bf16", 2 * D), ("fp8", D + 1)):
+            t = sorted(times[k])[len(times[k]) // 2]
+            res[f"{k}_us"] = round(t * 1e6, 1)
+            res[f"{k}_tbps"] = round(rows * per_row / t / 1e12, 2)
+            res[f"{k}_us_min_max"] = [round(min(times[k]) * 1e6, 1), round(max(times[k]) * 1e6, 1)]
+        res["time_ratio"] = round(res["fp8_us"] / res["bf16_us"], 3)
+        emit(**res)
+        del kc, vc, kd, vd
+
+
 def attn_scan():
     """Prefill attention at a fixed 16,384 tokens per launch, T = 256 .. 4096 per sequence, causal and
     full: separates the per-workgroup fixed cost (Q load, first K / V tile, epilogue) from the
@@ -357,6 +404,8 @@ if __name__ == "__main__":
                      tuple(int(m) for m in sys.argv[3].split(",")) if len(sys.argv) > 3 else (128,))
     if which == "decode":
         decode_sweep()
+    if which in ("decode", "decodefp8"):
+        decode_fp8_sweep()
     if which in ("all", "gemm"):
         gemm_suite(sys.argv[2] if len(sys.argv) > 2 else None)
     if which in ("all", "attn"):

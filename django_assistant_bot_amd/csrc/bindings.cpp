@@ -156,6 +156,33 @@ PYBIND11_MODULE(_native, m) {
      py::arg("Hkv"), py::arg("D"), py::arg("part_size"), py::arg("max_parts"), py::arg("scale"), py::arg("s"),
      py::arg("order") = 0, py::arg("w0") = 0, py::arg("w0_bytes") = 0, py::arg("w1") = 0, py::arg("w1_bytes") = 0,
      py::arg("w_blocks") = 0);
+  // FP8 KV cache (kv_fp8.hip)
+  m.def("rope_kv_write_fp8", [](u qkv, int ld, u positions, u cos_sin, u q_out, u k_data, u k_exp, u v_data, u v_exp,
+                                u slots, int T, int Hq, int Hkv, int D, int block_size, u s, u slabs, int S,
+                                long slab_stride, int slab_bf16) {
+    check(dab::rope_kv_write_fp8(CVP(qkv), ld, (const int*)positions, CVP(cos_sin), VP(q_out), VP(k_data), VP(k_exp),
+                                 VP(v_data), VP(v_exp), (const int64_t*)slots, T, Hq, Hkv, D, block_size, ST(s),
+                                 CVP(slabs), S, slab_stride, slab_bf16),
+          "rope_kv_write_fp8");
+  }, py::arg("qkv"), py::arg("ld"), py::arg("positions"), py::arg("cos_sin"), py::arg("q_out"), py::arg("k_data"),
+     py::arg("k_exp"), py::arg("v_data"), py::arg("v_exp"), py::arg("slots"), py::arg("T"), py::arg("Hq"),
+     py::arg("Hkv"), py::arg("D"), py::arg("block_size"), py::arg("s"), py::arg("slabs") = 0, py::arg("S") = 0,
+     py::arg("slab_stride") = 0, py::arg("slab_bf16") = 0);
+  m.def("kv_fp8_dequant_blocks", [](u k_data, u k_exp, u v_data, u v_exp, u ids, int n, u k_out, u v_out, int Hkv,
+                                    int block_size, int D, u s) {
+    check(dab::kv_fp8_dequant_blocks(CVP(k_data), CVP(k_exp), CVP(v_data), CVP(v_exp), (const int*)ids, n, VP(k_out),
+                                     VP(v_out), Hkv, block_size, D, ST(s)),
+          "kv_fp8_dequant_blocks");
+  });
+  m.def("paged_decode_attention_fp8", [](u q, u k_data, u k_exp, u v_data, u v_exp, u bt, int max_blocks, int bs, u ctx,
+                                         u out, u po, u pm, u pl, u cnt, int batch, int Hq, int Hkv, int D,
+                                         int part_size, int max_parts, float scale, u s, u order) {
+    check(dab::paged_decode_attention_fp8(CVP(q), CVP(k_data), CVP(k_exp), CVP(v_data), CVP(v_exp), (const int*)bt,
+                                          max_blocks, bs, (const int*)ctx, VP(out), (float*)po, (float*)pm, (float*)pl,
+                                          (int*)cnt, batch, Hq, Hkv, D, part_size, max_parts, scale, ST(s),
+                                          (const int*)order),
+          "paged_decode_attention_fp8");
+  });
   m.def("gemm_bt", [](u A, long lda, u B, long ldb, u C, long ldc, u bias, u residual, long ldr, int M, int N, int K,
                       int epilogue, int out_f32, u row_group, u q_group, u allow, int allow_words, u s, int b_rows,
                       int b_group) {

@@ -54,6 +54,22 @@ int paged_decode_attention(const void* q, const void* k_cache, const void* v_cac
                            int part_size, int max_parts, float scale, hipStream_t s,
                            const int* order = nullptr, const L3Warm* warm = nullptr);
 
+// kv_fp8.hip (opt-in FP8 KV cache, D = 128: e4m3fn data [blocks, Hkv, block_size, 128] and E8M0
+// exponent bytes [blocks, Hkv, block_size], for K and for V)
+int rope_kv_write_fp8(const void* qkv, int ld, const int* positions, const void* cos_sin, void* q_out, void* k_data,
+                      void* k_exp, void* v_data, void* v_exp, const int64_t* slots, int T, int Hq, int Hkv, int D,
+                      int block_size, hipStream_t s, const void* slabs = nullptr, int S = 0, long slab_stride = 0,
+                      int slab_bf16 = 0);
+// bf16 image of blocks block_ids[0..n) into k_out / v_out [n, Hkv, block_size, 128]
+int kv_fp8_dequant_blocks(const void* k_data, const void* k_exp, const void* v_data, const void* v_exp,
+                          const int* block_ids, int n, void* k_out, void* v_out, int Hkv, int block_size, int D,
+                          hipStream_t s);
+int paged_decode_attention_fp8(const void* q, const void* k_data, const void* k_exp, const void* v_data,
+                               const void* v_exp, const int* block_tables, int max_blocks, int block_size,
+                               const int* ctx_lens, void* out, float* part_o, float* part_m, float* part_l,
+                               int* counters, int batch, int Hq, int Hkv, int D, int part_size, int max_parts,
+                               float scale, hipStream_t s, const int* order = nullptr);
+
 // gemm.hip
 // b_rows > 0: B is an ops.shuffle_weights copy of b_rows (>= N) rows; epilogue 4 = SwiGLU over 8-row
 // [gate | up] groups

@@ -103,18 +103,33 @@ class LLMEngine:
                  max_prefill_tokens: int = 16384, use_graphs: bool = True, prefix_cache: bool = True,
                  tp_group=None, tp_size: int = 1, tp_rank: int = 0, interleaved_mlp: bool = True,
                  part_size: int = 512, kv_memory_fraction: float = 0.85, mixed_prefill_tokens: int = 0,
-                 pipeline_decode: bool = True, shared_model: LlamaModel | None = None):
+                 pipeline_decode: bool = True, shared_model: LlamaModel | None = None,
+                 kv_cache_dtype: str | None = None, kv_scratch_blocks: int | None = None):
         """``shared_model``: serve with another engine's ``LlamaModel`` (one copy of the weights, a
         KV pool / scheduler / HIP graphs of this engine's own; e.g. two engines on two streams whose
-        prefill and decode phases overlap: bench.py --mode overlap)."""
+        prefill and decode phases overlap: bench.py --mode overlap).
+
+        ``kv_cache_dtype``: ``"bf16"`` or ``"fp8"`` (opt-in FP8 KV cache: docs/ARCHITECTURE.md); ``None``
+        reads ``DAB_KV_CACHE_DTYPE`` from the environment, else bf16.  ``kv_scratch_blocks``: size of
+        the FP8 cache's bf16 prefill scratch (default: ``max(max_prefill_tokens, max_model_len) /
+        block_size + max_batch`` blocks)."""
         self.cfg = decoder_config(model) if isinstance(model, str) else model
         cfg = self.cfg
+        if kv_cache_dtype is None:
+            kv_cache_dtype = os.environ.get("DAB_KV_CACHE_DTYPE") or "bf16"
+        if kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype must be 'bf16' or 'fp8', got {kv_cache_dtype!r}")
+        if kv_cache_dtype == "fp8" and tp_size > 1:
+            raise ValueError("kv_cache_dtype='fp8' does not support tensor parallelism (tp_size > 1) yet")
+        self.kv_cache_dtype = kv_cache_dtype
         if checkpoint is None and weights is None and shared_model is None:
             from ..models.configs import checkpoint_dir
 
             checkpoint = checkpoint_dir(model)  # a local HF directory given as the model name
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.is_gpu = self.device.type == "cuda"
+        if kv_cache_dtype == "fp8" and self.is_gpu and cfg.head_dim != 128:  # (before any weight is built)
+            raise ValueError(f"kv_cache_dtype='fp8' needs head_dim 128 on the GPU (model has {cfg.head_dim})")
         self.tp_group, self.tp_size, self.tp_rank = tp_group, tp_size, tp_rank
         own_weights = weights is None  # a dict built here may be consumed while it is converted
         if shared_model is not None:
@@ -157,17 +172,26 @@ class LLMEngine:
         # batches need the finer split to give every CU work.
         self.long_part_size = max(part_size, 2048)
         hkv = cfg.kv_heads // tp_size
-        per_block = KVCache.bytes_per_block(cfg.layers, hkv, block_size, cfg.head_dim)
+        fp8 = kv_cache_dtype == "fp8"
+        per_block = KVCache.bytes_per_block(cfg.layers, hkv, block_size, cfg.head_dim, kv_dtype=kv_cache_dtype)
+        # FP8: the prefill attention reads a bf16 image of a step's context blocks from a scratch pool
+        # of this many blocks (>= one sequence; a step with more runs in groups of whole sequences)
+        scratch = 0
+        if fp8 and self.is_gpu:
+            scratch = kv_scratch_blocks or (math.ceil(max(max_prefill_tokens, self.max_model_len) / block_size) + max_batch)
+            scratch = max(int(scratch), self.max_blocks_per_seq)
         if num_blocks is None:
             if kv_cache_gb:
                 num_blocks = int(kv_cache_gb * (1 << 30) // per_block)
             elif self.is_gpu:
                 free, _ = torch.cuda.mem_get_info(self.device)
+                free -= KVCache.scratch_bytes(scratch, hkv, block_size, cfg.head_dim)
                 num_blocks = int(free * kv_memory_fraction // per_block)
             else:
                 num_blocks = 4 * self.max_blocks_per_seq
             num_blocks = max(2, min(num_blocks, max_batch * self.max_blocks_per_seq + 8))
-        self.kv = KVCache(cfg.layers, num_blocks, hkv, block_size, cfg.head_dim, self.device)
+        self.kv = KVCache(cfg.layers, num_blocks, hkv, block_size, cfg.head_dim, self.device, kv_dtype=kv_cache_dtype,
+                          scratch_blocks=scratch)
         self.blocks = native().KVBlockManager(num_blocks, block_size, prefix_cache)
         self._prefix_cache = prefix_cache
         self.seed = seed
@@ -177,7 +201,10 @@ class LLMEngine:
         self.finished: dict[int, _Req] = {}
         self._ids = itertools.count()
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "decode_steps": 0, "prefill_steps": 0,
-                      "preemptions": 0, "graph_replays": 0, "mixed_steps": 0}
+                      "preemptions": 0, "graph_replays": 0, "mixed_steps": 0,
+                      # the KV cache's element width (16: bf16, 8: fp8 = ``kv_cache_dtype``); a number like
+                      # every other entry, since consumers subtract two snapshots of this dict
+                      "kv_cache_bits": 8 if fp8 else 16}
         # decode static buffers (graph inputs / outputs)
         self.use_graphs = use_graphs and self.is_gpu
         dev = self.device
@@ -452,6 +479,14 @@ class LLMEngine:
     def _build_block_tables(self, seqs, out_host):
         self.blocks.block_table_into(seqs, self.max_blocks_per_seq, out_host.data_ptr())
 
+    def _kv_prefill_plan(self, bt, ctx, cu) -> dict:
+        """FP8 cache on the GPU: the step's dequantisation plan (``AttnMeta.kv_*``) from its host
+        block table / context lengths / cu_q; nothing otherwise."""
+        if not (self.kv.fp8 and self.is_gpu):
+            return {}
+        p = ops.kv_prefill_plan(bt, ctx, cu, self.block_size, self.kv.scratch_blocks, self.device)
+        return {"kv_blocks": p.blocks, "kv_scratch_bt": p.scratch_bt, "kv_groups": p.groups}
+
     def _run_prefill(self, chunks):
         t0 = time.perf_counter()
         B = len(chunks)
@@ -474,7 +509,7 @@ class LLMEngine:
         self._build_block_tables([r.seq for r, _, _ in chunks], bt)
         to = self._h2d
         meta = AttnMeta(decode=False, positions=to(pos), slots=to(slots), block_tables=to(bt), ctx_lens=to(ctx),
-                        cu_q=to(cu), max_q=max(n for _, _, n in chunks))
+                        cu_q=to(cu), max_q=max(n for _, _, n in chunks), **self._kv_prefill_plan(bt, ctx, cu))
         # only the last row of each prompt that ends here is read: the model runs the last layer's
         # row-wise tail on those rows alone where it can (``LlamaModel.forward`` ``out_rows``)
         last_rows = [i for i, (r, s, n) in enumerate(chunks) if s + n == len(r.full_prompt())]
@@ -583,7 +618,7 @@ class LLMEngine:
         meta = AttnMeta(decode=False, positions=to(pos), slots=to(slots), block_tables=to(bt), ctx_lens=to(ctx),
                         cu_q=to(cu), max_q=max(n for _, _, n in chunks), workspace=self._workspace,
                         part_size=self._decode_part(Bp), n_decode=Bp, dec_block_tables=self._d_bt[:Bp],
-                        dec_ctx_lens=self._d_ctx[:Bp], order=order)
+                        dec_ctx_lens=self._d_ctx[:Bp], order=order, **self._kv_prefill_plan(bt, ctx, cu))
         last_rows = [i for i, (r, s, n) in enumerate(chunks) if s + n == len(r.full_prompt())]
         sel = [int(cu[i + 1]) - 1 for i in last_rows] + list(range(Tp, Tp + B))
         sel_d = torch.as_tensor(sel, dtype=torch.int32).to(dev, non_blocking=True)

@@ -58,6 +58,12 @@ class AttnMeta:
     dec_ctx_lens: torch.Tensor | None = None
     order: torch.Tensor | None = None  # int32 [B] decode attention dispatch order (longest context first;
     # of the decode rows in a mixed step)
+    # FP8 KV cache, prefill rows (``ops.kv_prefill_plan``, built once per step on the host): the
+    # step's context blocks group after group, the block table into the bf16 scratch they are
+    # dequantised to, and the groups of whole sequences that fit the scratch
+    kv_blocks: torch.Tensor | None = None
+    kv_scratch_bt: torch.Tensor | None = None
+    kv_groups: list | None = None
 
 
 class _Partial:
@@ -72,16 +78,83 @@ class _Partial:
 
 
 class KVCache:
-    """Paged KV cache: per layer [num_blocks, Hkv_local, block_size, D] for K and for V."""
+    """Paged KV cache: per layer [num_blocks, Hkv_local, block_size, D] for K and for V.
 
-    def __init__(self, layers, num_blocks, kv_heads, block_size, head_dim, device, dtype=torch.bfloat16):
+    ``kv_dtype="fp8"`` (opt-in, D = 128 on the GPU): ``k`` / ``v`` hold OCP e4m3fn bytes (uint8) and
+    ``k_exp`` / ``v_exp`` [layers, num_blocks, Hkv, block_size] one power-of-two exponent byte per
+    (token, kv head) row (docs/ARCHITECTURE.md "FP8 KV cache").  The prefill attention reads a bf16
+    image of the step's context blocks from ``scratch_k`` / ``scratch_v`` [scratch_blocks, Hkv,
+    block_size, D], one layer at a time; the scratch belongs to the cache (hence to the engine): two
+    engines sharing one model on two streams each dequantise into their own.
+
+    Every cache touch of the model goes through ``write``, ``decode_attention`` and
+    ``prefill_attention``."""
+
+    def __init__(self, layers, num_blocks, kv_heads, block_size, head_dim, device, dtype=torch.bfloat16,
+                 kv_dtype: str = "bf16", scratch_blocks: int = 0):
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         self.num_blocks, self.block_size = num_blocks, block_size
-        self.k = torch.zeros((layers, num_blocks, kv_heads, block_size, head_dim), device=device, dtype=dtype)
+        self.kv_dtype = kv_dtype
+        self.fp8 = kv_dtype == "fp8"
+        self.k_exp = self.v_exp = self.scratch_k = self.scratch_v = None
+        self.scratch_blocks = 0
+        if not self.fp8:
+            self.k = torch.zeros((layers, num_blocks, kv_heads, block_size, head_dim), device=device, dtype=dtype)
+            self.v = torch.zeros_like(self.k)
+            return
+        dev = torch.device(device)
+        if dev.type == "cuda" and head_dim != 128:
+            raise ValueError("the FP8 KV cache kernels take head_dim 128 only")
+        self.k = torch.zeros((layers, num_blocks, kv_heads, block_size, head_dim), device=dev, dtype=torch.uint8)
         self.v = torch.zeros_like(self.k)
+        # exponent 127 (scale 1) over zero bytes: an untouched slot reads as 0.0
+        self.k_exp = torch.full((layers, num_blocks, kv_heads, block_size), 127, device=dev, dtype=torch.uint8)
+        self.v_exp = torch.full_like(self.k_exp, 127)
+        if dev.type == "cuda":
+            self.scratch_blocks = max(1, int(scratch_blocks) or num_blocks)
+            self.scratch_k = torch.zeros((self.scratch_blocks, kv_heads, block_size, head_dim), device=dev, dtype=dtype)
+            self.scratch_v = torch.zeros_like(self.scratch_k)
 
     @staticmethod
-    def bytes_per_block(layers, kv_heads, block_size, head_dim, dtype=torch.bfloat16):
+    def bytes_per_block(layers, kv_heads, block_size, head_dim, dtype=torch.bfloat16, kv_dtype: str = "bf16"):
+        if kv_dtype == "fp8":  # data + one exponent byte per row
+            return 2 * layers * kv_heads * block_size * (head_dim + 1)
         return 2 * layers * kv_heads * block_size * head_dim * torch.finfo(dtype).bits // 8
+
+    @staticmethod
+    def scratch_bytes(scratch_blocks, kv_heads, block_size, head_dim, dtype=torch.bfloat16):
+        return 2 * scratch_blocks * kv_heads * block_size * head_dim * torch.finfo(dtype).bits // 8
+
+    def write(self, li, qkv, positions, cos_sin, slots, Hq, Hkv, D, write_q=True):
+        """RoPE on q / k and the cache write of layer ``li``: -> q [T, Hq, D] (None: ``write_q`` off)."""
+        if self.fp8:
+            return ops.rope_kv_write_fp8(qkv, positions, cos_sin, self.k[li], self.k_exp[li], self.v[li], self.v_exp[li],
+                                         slots, Hq, Hkv, D, write_q=write_q)
+        return ops.rope_kv_write(qkv, positions, cos_sin, self.k[li], self.v[li], slots, Hq, Hkv, D, write_q=write_q)
+
+    def decode_attention(self, li, q, block_tables, ctx_lens, part_size, workspace, out=None, order=None, warm=None):
+        if self.fp8:  # (``warm``: refused by the FP8 op)
+            return ops.paged_decode_fp8(q, self.k[li], self.k_exp[li], self.v[li], self.v_exp[li], block_tables, ctx_lens,
+                                        part_size, workspace, out=out, order=order, warm=warm)
+        return ops.paged_decode(q, self.k[li], self.v[li], block_tables, ctx_lens, part_size, workspace, out=out,
+                                order=order, warm=warm)
+
+    def prefill_attention(self, li, q, meta, out=None, rope=None):
+        """Causal prefill attention of the step's prefill rows ``q`` over layer ``li``."""
+        if not self.fp8:
+            return ops.flash_attention_paged(q, self.k[li], self.v[li], meta.block_tables, meta.cu_q, meta.ctx_lens,
+                                             meta.max_q, causal=True, out=out, rope=rope)
+        plan = None
+        if q.is_cuda:
+            if meta.kv_groups is None:  # a caller without a host plan (tests, tools): built once, synchronises
+                p = ops.kv_prefill_plan(meta.block_tables, meta.ctx_lens, meta.cu_q, self.block_size,
+                                        self.scratch_blocks, q.device)
+                meta.kv_blocks, meta.kv_scratch_bt, meta.kv_groups = p.blocks, p.scratch_bt, p.groups
+            plan = ops.KVPrefillPlan(meta.kv_blocks, meta.kv_scratch_bt, meta.kv_groups)
+        return ops.flash_attention_paged_fp8(q, self.k[li], self.k_exp[li], self.v[li], self.v_exp[li], meta.block_tables,
+                                             meta.cu_q, meta.ctx_lens, meta.max_q, causal=True, out=out, rope=rope,
+                                             scratch=(self.scratch_k, self.scratch_v), plan=plan)
 
 
 class LlamaModel:
@@ -311,7 +384,15 @@ class LlamaModel:
     # fp32 slabs.
     slab_bf16 = True
 
-    def _proj(self, x, w, dec: bool, allow_slabs: bool = True, name: str = "", epilogue=ops.EPI_NONE):
+    # FP8 KV cache: the qkv projection keeps fp32 split-K slabs.  A bf16 slab rounds every partial sum, which
+    # leaves ~40 % of the K / V values one bf16 step away from the MFMA GEMM's; the quantiser turns such a step
+    # into a whole FP8 step (16 bf16 steps) wherever it crosses a rounding boundary, so a streamed step and a
+    # GEMM step (a short prefill against a mixed step, a decode step against a prefill) would cache visibly
+    # different bytes for the same token: ~1.8k of 31k K bytes against 0-1 with fp32 slabs (profiles/kv_fp8.md).
+    fp8_qkv_slab_f32 = True
+
+    def _proj(self, x, w, dec: bool, allow_slabs: bool = True, name: str = "", epilogue=ops.EPI_NONE,
+              slab_f32: bool = False):
         """One projection.  Decode-sized batches (``dec``) stream the fragment-layout weights
         through stream_gemm, as fp32 split-K slabs when a consumer sums them (RMSNorm, the decode
         attention's RoPE prologue) and ``allow_slabs``; everything else runs the MFMA GEMM on the
@@ -327,7 +408,7 @@ class LlamaModel:
             if cfg >= 0:
                 if epilogue != ops.EPI_NONE:
                     return ops.stream_gemm(x, w, epilogue=epilogue, nt=True, cfg=cfg, w_group=grp)
-                sd = torch.bfloat16 if (self.slab_bf16 and self.tp_size == 1) else torch.float32
+                sd = torch.bfloat16 if (self.slab_bf16 and self.tp_size == 1 and not slab_f32) else torch.float32
                 out = ops.stream_gemm(x, w, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp)
                 return ops.slab_reduce(out) if (s > 1 and not allow_slabs) else out
         return ops.gemm_bt(x, w, epilogue=epilogue, shuffled=self.frag, b_group=grp)
@@ -403,9 +484,9 @@ class LlamaModel:
         c, s = self._stream_choice("qkv", T, L.qkv_w.shape[0], L.qkv_w.shape[1])
         pg = self.proj_group
         qkv = ops.stream_gemm(h, L.qkv_w, splits=s, cfg=c, nt=True, norm_eps=cfg.eps, w_group=pg.get("qkv", 1))
-        q = ops.rope_kv_write(qkv, meta.positions, self.cos_sin, kv.k[li], kv.v[li], meta.slots, self.hq, self.hkv, D)
-        a = ops.paged_decode(q, kv.k[li], kv.v[li], meta.block_tables, meta.ctx_lens, meta.part_size,
-                             meta.workspace, order=meta.order)
+        q = kv.write(li, qkv, meta.positions, self.cos_sin, meta.slots, self.hq, self.hkv, D)
+        a = kv.decode_attention(li, q, meta.block_tables, meta.ctx_lens, meta.part_size, meta.workspace,
+                                order=meta.order)
         h1 = ops.stream_gemm(a.view(T, self.hq * D), L.o_w, residual=h, cfg=self.STREAM_CFG_RES16, nt=True,
                              w_group=pg.get("o", 1))
         gc, _ = self._stream_choice("gate_up", T, L.gate_up_w.shape[0], L.gate_up_w.shape[1])
@@ -477,28 +558,25 @@ class LlamaModel:
             residual = x
         else:
             h, residual = self._norm(x, L.attn_norm, residual)
-        qkv = self._proj(h, L.qkv_w, sk, name="qkv")
+        qkv = self._proj(h, L.qkv_w, sk, name="qkv", slab_f32=kv.fp8 and self.fp8_qkv_slab_f32)
         if (not meta.decode and not meta.n_decode and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 2
                 and ops.kernels.flash_rope_ok(D, kv.block_size)):
             # prefill: the RoPE/KV-write kernel writes only K / V; the attention rotates Q on load
             # straight from the projection (a [T, Hq*D] write and read less per layer)
-            ops.rope_kv_write(qkv, meta.positions, self.cos_sin, kv.k[li], kv.v[li], meta.slots, self.hq, self.hkv, D,
-                              write_q=False)
+            kv.write(li, qkv, meta.positions, self.cos_sin, meta.slots, self.hq, self.hkv, D, write_q=False)
             q = qkv[:, :self.hq * D].view(T, self.hq, D)
-            a = ops.flash_attention_paged(q, kv.k[li], kv.v[li], meta.block_tables, meta.cu_q, meta.ctx_lens,
-                                          meta.max_q, causal=True, rope=(meta.positions, self.cos_sin))
+            a = kv.prefill_attention(li, q, meta, rope=(meta.positions, self.cos_sin))
             if rows is not None:
                 return self._layer_tail_rows(L, a, residual, rows, T, D)
             return self._layer_tail(L, a, residual, sk, fuse, slabs_ok, T, D)
-        q = ops.rope_kv_write(qkv, meta.positions, self.cos_sin, kv.k[li], kv.v[li], meta.slots, self.hq, self.hkv, D)
+        q = kv.write(li, qkv, meta.positions, self.cos_sin, meta.slots, self.hq, self.hkv, D)
         if meta.decode:
-            a = ops.paged_decode(q, kv.k[li], kv.v[li], meta.block_tables, meta.ctx_lens, meta.part_size,
-                                 meta.workspace, order=meta.order, warm=self._warm(L, T, q))
+            a = kv.decode_attention(li, q, meta.block_tables, meta.ctx_lens, meta.part_size, meta.workspace,
+                                    order=meta.order, warm=self._warm(L, T, q))
         elif meta.n_decode:
             a = self._mixed_attention(q, kv, li, meta)
         else:
-            a = ops.flash_attention_paged(q, kv.k[li], kv.v[li], meta.block_tables, meta.cu_q, meta.ctx_lens,
-                                          meta.max_q, causal=True)
+            a = kv.prefill_attention(li, q, meta)
         if rows is not None:
             return self._layer_tail_rows(L, a, residual, rows, T, D)
         return self._layer_tail(L, a, residual, sk, fuse, slabs_ok, T, D)
@@ -555,17 +633,15 @@ class LlamaModel:
         if not q.is_cuda:
             parts = []
             if Tp:
-                parts.append(ops.flash_attention_paged(q[:Tp], kv.k[li], kv.v[li], meta.block_tables, meta.cu_q,
-                                                       meta.ctx_lens, meta.max_q, causal=True))
-            parts.append(ops.paged_decode(q[Tp:], kv.k[li], kv.v[li], meta.dec_block_tables, meta.dec_ctx_lens,
-                                          meta.part_size, meta.workspace))
+                parts.append(kv.prefill_attention(li, q[:Tp], meta))
+            parts.append(kv.decode_attention(li, q[Tp:], meta.dec_block_tables, meta.dec_ctx_lens, meta.part_size,
+                                             meta.workspace))
             return torch.cat(parts)
         a = torch.empty_like(q)
         if Tp:
-            ops.flash_attention_paged(q[:Tp], kv.k[li], kv.v[li], meta.block_tables, meta.cu_q, meta.ctx_lens,
-                                      meta.max_q, causal=True, out=a[:Tp])
-        ops.paged_decode(q[Tp:], kv.k[li], kv.v[li], meta.dec_block_tables, meta.dec_ctx_lens, meta.part_size,
-                         meta.workspace, out=a[Tp:], order=meta.order)
+            kv.prefill_attention(li, q[:Tp], meta, out=a[:Tp])
+        kv.decode_attention(li, q[Tp:], meta.dec_block_tables, meta.dec_ctx_lens, meta.part_size, meta.workspace,
+                            out=a[Tp:], order=meta.order)
         return a
 
     def logits(self, h: torch.Tensor) -> torch.Tensor:

@@ -339,6 +339,209 @@ def paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, part_size=512, wor
 
 
 # ----------------------------------------------------------------------------------------------
+# FP8 KV cache (opt-in; kv_fp8.hip).  Data uint8 [num_blocks, Hkv, block_size, 128] (OCP e4m3fn),
+# exponents uint8 [num_blocks, Hkv, block_size] (E8M0: value = byte * 2^(b - 127)), K and V alike.
+
+kv_quantize = ref.kv_quantize
+kv_dequantize = ref.kv_dequantize
+
+
+def _expect_fp8_cache(k_data, k_exp, v_data, v_exp):
+    for t in (k_data, k_exp, v_data, v_exp):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise TypeError("the FP8 KV cache is contiguous uint8 (data and exponent bytes)")
+    same_device(k_data, k_exp, v_data, v_exp)
+    expect(k_data.dim() == 4 and k_data.shape == v_data.shape and tuple(k_exp.shape) == tuple(k_data.shape[:3])
+           and k_exp.shape == v_exp.shape, "FP8 cache: data [blocks, Hkv, block_size, D], exponents [blocks, Hkv, block_size]")
+    expect(k_data.shape[3] == 128, "the FP8 KV cache kernels take head dim 128 only")
+
+
+def rope_kv_write_fp8(qkv, positions, cos_sin, k_data, k_exp, v_data, v_exp, slots, Hq, Hkv, D, write_q=True):
+    """``rope_kv_write`` into an FP8 cache: each k / v head row is quantised from the value the bf16
+    cache would hold (k: rotated, rounded to bf16); q is returned exactly as ``rope_kv_write`` does."""
+    block_size = k_data.shape[2]
+    slabs = qkv.dim() == 3 and qkv.dtype in (torch.float32, torch.bfloat16)
+    if not qkv.is_cuda:
+        if slabs:
+            qkv = qkv.float().sum(0).to(torch.bfloat16)
+        q = ref.rope_kv_write_fp8(qkv, positions, cos_sin, k_data, k_exp, v_data, v_exp, slots, Hq, Hkv, D, block_size)
+        return q if write_q else None
+    expect(D == 128, "the FP8 KV cache kernels take head dim 128 only")
+    _expect_fp8_cache(k_data, k_exp, v_data, v_exp)
+    _i32(positions)
+    expect(slots.dtype == torch.int64 and slots.is_contiguous(), "slots must be contiguous int64")
+    expect(cos_sin.dtype == torch.float32 and cos_sin.is_contiguous(), "cos_sin must be contiguous fp32")
+    T = qkv.shape[-2]
+    expect(qkv.shape[-1] == (Hq + 2 * Hkv) * D, "qkv width mismatch")
+    expect(positions.numel() == T and slots.numel() == T, "positions / slots length mismatch")
+    expect(k_data.shape[1] == Hkv, "cache shape mismatch")
+    expect(cos_sin.shape[1] == D // 2, "cos/sin table width mismatch")
+    caches = (ptr(k_data), ptr(k_exp), ptr(v_data), ptr(v_exp))
+    if not write_q:
+        expect(not slabs, "write_q=False needs a bf16 qkv")
+        expect_bf16_contig(qkv)
+        native().rope_kv_write_fp8(ptr(qkv), qkv.stride(0), ptr(positions), ptr(cos_sin), 0, *caches, ptr(slots), T,
+                                   Hq, Hkv, D, block_size, stream(qkv))
+        return None
+    q = torch.empty((T, Hq, D), dtype=torch.bfloat16, device=qkv.device)
+    if slabs:
+        expect(qkv.is_contiguous(), "slabs must be contiguous")
+        native().rope_kv_write_fp8(0, qkv.shape[-1], ptr(positions), ptr(cos_sin), ptr(q), *caches, ptr(slots), T, Hq,
+                                   Hkv, D, block_size, stream(qkv), ptr(qkv), qkv.shape[0], T * qkv.shape[-1],
+                                   int(qkv.dtype == torch.bfloat16))
+    else:
+        expect_bf16_contig(qkv)
+        native().rope_kv_write_fp8(ptr(qkv), qkv.stride(0), ptr(positions), ptr(cos_sin), ptr(q), *caches, ptr(slots),
+                                   T, Hq, Hkv, D, block_size, stream(qkv))
+    return q
+
+
+def paged_decode_fp8(q, k_data, k_exp, v_data, v_exp, block_tables, ctx_lens, part_size=512,
+                     workspace: DecodeWorkspace | None = None, scale=None, out=None, order=None, warm=None):
+    """``paged_decode`` over an FP8 cache (D = 128): the same dispatch, partitions, ``order``,
+    workspace and in-launch combine; FP8 -> bf16 in registers, bf16 MFMA.  ``warm`` is not supported."""
+    B, Hq, D = q.shape
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    expect(warm is None, "paged_decode_fp8 does not take warm= (the L3 warm-up rides on the bf16 kernel only)")
+    if not q.is_cuda:
+        return ref.paged_decode_fp8(q, k_data, k_exp, v_data, v_exp, block_tables, ctx_lens, scale)
+    expect(D == 128, "the FP8 KV cache kernels take head dim 128 only")
+    _i32(ctx_lens)
+    _i32(block_tables)
+    expect_bf16_contig(q)
+    _expect_fp8_cache(k_data, k_exp, v_data, v_exp)
+    Hkv, bs = k_data.shape[1], k_data.shape[2]
+    expect(bs % 32 == 0, "block size must be a multiple of 32")
+    expect(Hq % Hkv == 0 and Hq // Hkv <= 16, "GQA group must be <= 16")
+    expect(part_size % 128 == 0, "part_size must be a multiple of 128")
+    expect(block_tables.shape[0] >= B and ctx_lens.numel() >= B, "block table / ctx_lens rows < batch")
+    max_parts = workspace.max_parts if workspace is not None else 1
+    if workspace is None:
+        part_size = max(part_size, ((block_tables.shape[1] * bs + 127) // 128) * 128)
+        ws_o = ws_m = ws_l = ws_c = None
+    else:
+        expect(workspace.o.numel() >= B * Hq * max_parts * D and workspace.cnt.numel() >= B * Hkv,
+               "decode workspace too small")
+        ws_o, ws_m, ws_l, ws_c = workspace.o, workspace.m, workspace.l, workspace.cnt
+    out = torch.empty_like(q) if out is None else out
+    expect(out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == q.shape, "out: contiguous bf16 like q")
+    if order is not None:
+        _i32(order)
+        expect(order.is_cuda and order.numel() >= B, "decode order must hold the batch")
+    native().paged_decode_attention_fp8(ptr(q), ptr(k_data), ptr(k_exp), ptr(v_data), ptr(v_exp), ptr(block_tables),
+                                        block_tables.shape[1], bs, ptr(ctx_lens), ptr(out), ptr(ws_o), ptr(ws_m),
+                                        ptr(ws_l), ptr(ws_c), B, Hq, Hkv, D, int(part_size), int(max_parts),
+                                        float(scale), stream(q), ptr(order))
+    return out
+
+
+def kv_dequant_blocks(k_data, k_exp, v_data, v_exp, block_ids, k_out, v_out):
+    """k_out[i], v_out[i] ([cap, Hkv, block_size, D] bf16, cap >= n) = the bf16 image of block
+    ``block_ids[i]`` (int32 [n]) of an FP8 cache; rows past n are not touched."""
+    n = block_ids.numel()
+    expect(k_out.shape == v_out.shape and k_out.shape[0] >= n and tuple(k_out.shape[1:]) == tuple(k_data.shape[1:]),
+           "scratch: [cap >= n, Hkv, block_size, D]")
+    if not k_data.is_cuda:
+        ref.kv_dequant_blocks(k_data, k_exp, block_ids, k_out)
+        ref.kv_dequant_blocks(v_data, v_exp, block_ids, v_out)
+        return k_out, v_out
+    _expect_fp8_cache(k_data, k_exp, v_data, v_exp)
+    _i32(block_ids)
+    expect_bf16_contig(k_out, v_out)
+    same_device(k_data, block_ids, k_out, v_out)
+    native().kv_fp8_dequant_blocks(ptr(k_data), ptr(k_exp), ptr(v_data), ptr(v_exp), ptr(block_ids), n, ptr(k_out),
+                                   ptr(v_out), k_data.shape[1], k_data.shape[2], k_data.shape[3], stream(k_data))
+    return k_out, v_out
+
+
+class KVPrefillPlan:
+    """Host-built plan of one prefill step over an FP8 cache: the step's context blocks are
+    dequantised into a bf16 scratch pool and the prefill attention runs on the scratch with a
+    remapped block table.  ``blocks`` int32 [n]: the cache blocks, group after group; ``scratch_bt``
+    int32 [B, cols]: per sequence a running index into its group's scratch (padding columns repeat
+    a valid index); ``groups``: runs of whole sequences whose blocks fit the scratch --
+    (seq_lo, seq_hi, blk_lo, blk_hi, tok_lo, tok_hi, max_q, cu_q of the group or None for the only one)."""
+
+    __slots__ = ("blocks", "scratch_bt", "groups")
+
+    def __init__(self, blocks, scratch_bt, groups):
+        self.blocks, self.scratch_bt, self.groups = blocks, scratch_bt, groups
+
+
+def kv_prefill_plan(block_tables, ctx_lens, cu_q, block_size: int, cap: int, device=None) -> KVPrefillPlan:
+    """``block_tables`` [B, cols], ``ctx_lens`` [B], ``cu_q`` [B + 1]: host (or device: synchronises)
+    integer tensors / arrays of the step."""
+    bt = torch.as_tensor(block_tables).cpu()
+    ctx = [int(x) for x in torch.as_tensor(ctx_lens).cpu().tolist()]
+    cu = [int(x) for x in torch.as_tensor(cu_q).cpu().tolist()]
+    B = len(cu) - 1
+    nblk = [-(-ctx[b] // block_size) for b in range(B)]
+    cols = max(1, bt.shape[1])
+    sbt = torch.zeros((B, cols), dtype=torch.int32)
+    blocks, groups = [], []
+    lo = 0
+    while lo < B:
+        expect(nblk[lo] <= cap, f"a sequence of {nblk[lo]} KV blocks exceeds the FP8 prefill scratch ({cap} blocks)")
+        hi, used = lo, 0
+        while hi < B and used + nblk[hi] <= cap:
+            used += nblk[hi]
+            hi += 1
+        blk_lo, run = len(blocks), 0
+        for b in range(lo, hi):
+            blocks.extend(bt[b, :nblk[b]].tolist())
+            sbt[b, :nblk[b]] = torch.arange(run, run + nblk[b], dtype=torch.int32)
+            sbt[b, nblk[b]:] = run if nblk[b] else 0  # padding columns: any index the group wrote
+            run += nblk[b]
+        groups.append([lo, hi, blk_lo, len(blocks), cu[lo], cu[hi], max(cu[b + 1] - cu[b] for b in range(lo, hi))])
+        lo = hi
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+
+    def to(t):
+        if dev.type != "cuda":
+            return t
+        return t.pin_memory().to(dev, non_blocking=True)
+
+    single = len(groups) == 1
+    out_groups = []
+    for g in groups:
+        cu_g = None if single else to(torch.tensor([c - g[4] for c in cu[g[0]:g[1] + 1]], dtype=torch.int32))
+        out_groups.append((*g, cu_g))
+    return KVPrefillPlan(to(torch.tensor(blocks, dtype=torch.int32)), to(sbt), out_groups)
+
+
+def flash_attention_paged_fp8(q, k_data, k_exp, v_data, v_exp, block_tables, cu_q, ctx_lens, max_seqlen_q, causal=True,
+                              scale=None, out=None, rope=None, scratch=None, plan: KVPrefillPlan | None = None):
+    """``flash_attention_paged`` over an FP8 cache.  On the GPU the blocks of ``plan`` (built from
+    the step's host arrays: ``kv_prefill_plan``; built here, with a device synchronisation, when it
+    is missing) are dequantised into ``scratch`` = (k, v) bf16 [cap, Hkv, block_size, D] and the
+    unchanged bf16 prefill kernels run on it, group after group."""
+    if not q.is_cuda:
+        D = q.shape[-1]
+        scale = 1.0 / math.sqrt(D) if scale is None else scale
+        if rope is not None:
+            q = ref.rope_q(q.reshape(q.shape[0], q.shape[1], D), rope[0], rope[1])
+        res = ref.flash_attention_paged_fp8(q, k_data, k_exp, v_data, v_exp, block_tables, cu_q, ctx_lens, causal, scale)
+        return res if out is None else out.copy_(res)
+    expect(scratch is not None, "the FP8 prefill attention needs the cache's bf16 scratch pool")
+    sk, sv = scratch
+    if plan is None:
+        plan = kv_prefill_plan(block_tables, ctx_lens, cu_q, k_data.shape[2], sk.shape[0], q.device)
+    Hq, D = q.shape[1], q.shape[2]
+    out = torch.empty((q.shape[0], Hq, D), dtype=q.dtype, device=q.device) if out is None else out
+    for lo, hi, b0, b1, t0, t1, max_q, cu_g in plan.groups:
+        kv_dequant_blocks(k_data, k_exp, v_data, v_exp, plan.blocks[b0:b1], sk, sv)
+        if cu_g is None:  # the whole step: the very launch the bf16 cache would get
+            flash_attention_paged(q, sk, sv, plan.scratch_bt, cu_q, ctx_lens, max_seqlen_q, causal, scale, out, rope)
+            continue
+        if t1 == t0:
+            continue
+        r = None if rope is None else (rope[0][t0:t1], rope[1])
+        flash_attention_paged(q[t0:t1], sk, sv, plan.scratch_bt[lo:hi], cu_g, ctx_lens[lo:hi], max_q, causal, scale,
+                              out[t0:t1], r)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # GEMM
 
 

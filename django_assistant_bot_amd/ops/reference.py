@@ -161,6 +161,95 @@ def paged_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# FP8 KV cache (opt-in): per (token, kv head) row of D values, OCP e4m3fn data bytes and one E8M0
+# exponent byte b (scale 2^(b - 127)), K and V alike.  docs/ARCHITECTURE.md "FP8 KV cache".
+
+KV_FP8_MAX = 448.0
+
+
+def kv_quantize(x):
+    """bf16 (or bf16-exact) rows [..., D] -> (e4m3fn bytes uint8 [..., D], exponent bytes uint8 [...]).
+
+    The scale is the smallest power of two 2^e with amax / 2^e <= 448, found with integer operations
+    on the bits of amax (so the GPU writer agrees bit for bit): with amax = 1.M x 2^(E - 127) it is
+    e = E - 135, or E - 134 when 1.M > 1.75.  b = clamp(e + 127, 1, 254); a zero row has b = 127 and
+    zero bytes.  Data: x / 2^(b - 127) (exact), clamped to +-448, rounded to nearest-even."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    bits = amax.contiguous().view(torch.int32)
+    E, M = (bits >> 23) & 0xFF, bits & 0x7FFFFF
+    b = (E - 8 + (M > 0x600000).to(torch.int32)).clamp(1, 254)
+    b = torch.where(amax == 0, torch.full_like(b, 127), b)
+    inv = ((254 - b) << 23).view(torch.float32)  # 2^-(b - 127)
+    y = (xf * inv[..., None]).clamp(-KV_FP8_MAX, KV_FP8_MAX)
+    data = y.to(torch.float8_e4m3fn).view(torch.uint8)
+    data = torch.where((amax == 0)[..., None], torch.zeros_like(data), data)
+    return data, b.to(torch.uint8)
+
+
+def kv_dequantize(data, exps):
+    """(bytes [..., D], exponent bytes [...]) -> fp32 [..., D]; every value is bf16-exact."""
+    scale = (exps.to(torch.int32) << 23).view(torch.float32)
+    return data.view(torch.float8_e4m3fn).float() * scale[..., None]
+
+
+def rope_kv_write_fp8(qkv, positions, cos_sin, k_data, k_exp, v_data, v_exp, slots, Hq, Hkv, D, block_size):
+    """``rope_kv_write`` into an FP8 cache: what the bf16 cache would hold is quantised per row."""
+    T = qkv.shape[0]
+    kb = torch.zeros((1, Hkv, T, D), dtype=qkv.dtype, device=qkv.device)
+    vb = torch.zeros_like(kb)
+    q = rope_kv_write(qkv, positions, cos_sin, kb, vb, torch.arange(T, device=qkv.device), Hq, Hkv, D, T)
+    # (an fp32 model on the CPU: the bf16 rounding the GPU cache would hold is quantised)
+    kd, ke = kv_quantize(kb[0].to(torch.bfloat16))  # [Hkv, T, D], [Hkv, T]
+    vd, ve = kv_quantize(vb[0].to(torch.bfloat16))
+    for t in range(T):
+        s = int(slots[t])
+        if s < 0:
+            continue
+        blk, off = divmod(s, block_size)
+        k_data[blk, :, off], k_exp[blk, :, off] = kd[:, t], ke[:, t]
+        v_data[blk, :, off], v_exp[blk, :, off] = vd[:, t], ve[:, t]
+    return q
+
+
+def kv_dequant_blocks(data, exps, block_ids, out):
+    """out[i] = bf16 image of block ``block_ids[i]`` (data [blocks, Hkv, bs, D], exps [blocks, Hkv, bs])."""
+    idx = block_ids.long()
+    out[: idx.numel()] = kv_dequantize(data[idx], exps[idx]).to(out.dtype)
+    return out
+
+
+def gather_paged_fp8(data, exps, block_table, n):
+    """The first n tokens of a sequence, dequantised on gather: fp32 [n, Hkv, D]."""
+    bs = data.shape[2]
+    idx = block_table[: (n + bs - 1) // bs].long()
+    blocks = kv_dequantize(data[idx], exps[idx])  # [nb, Hkv, bs, D]
+    return blocks.permute(0, 2, 1, 3).reshape(idx.numel() * bs, data.shape[1], data.shape[3])[:n]
+
+
+def flash_attention_paged_fp8(q, k_data, k_exp, v_data, v_exp, block_tables, cu_q, ctx_lens, causal, scale):
+    out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    cq = cu_q.tolist()
+    for b in range(len(cq) - 1):
+        n = int(ctx_lens[b])
+        ks = gather_paged_fp8(k_data, k_exp, block_tables[b], n)
+        vs = gather_paged_fp8(v_data, v_exp, block_tables[b], n)
+        qs = q[cq[b]:cq[b + 1]]
+        out[cq[b]:cq[b + 1]] = _attend(qs, ks, vs, scale, causal, n - qs.shape[0]).to(q.dtype)
+    return out
+
+
+def paged_decode_fp8(q, k_data, k_exp, v_data, v_exp, block_tables, ctx_lens, scale):
+    out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    for b in range(q.shape[0]):
+        n = int(ctx_lens[b])
+        ks = gather_paged_fp8(k_data, k_exp, block_tables[b], n)
+        vs = gather_paged_fp8(v_data, v_exp, block_tables[b], n)
+        out[b] = _attend(q[b:b + 1], ks, vs, scale, False, 0)[0].to(q.dtype)
+    return out
+
+
 def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, row_group=None, q_group=None,
             allow=None):
     c = A.float() @ B.float().t()

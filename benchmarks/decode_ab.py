@@ -98,6 +98,14 @@ ARMS = {
     "gu42": {"gate_up": (42, 1)},
     # the opt-in FP8 KV cache: a second engine on the same model (its own pool, scheduler and graphs)
     "kvfp8": {"_kv": "fp8"},
+    # the opt-in FP8 projection weights.  With any "_w" arm the one model is built with
+    # weight_dtype="fp8" (FP8 copies + bf16 copies of the dequantised values); arms without "_w"
+    # stream the bf16 copies (``LlamaModel.fp8_stream`` off: the default model's code path on the
+    # same values), "_w" arms the FP8 copies; "_ring" 1: the FP8 arm's doubled weight ring
+    "wfp8": {"_w": "fp8"},
+    "wfp8_deep": {"_w": "fp8", "_ring": 1},
+    "wkvfp8": {"_w": "fp8", "_kv": "fp8"},
+    "wkvfp8_deep": {"_w": "fp8", "_kv": "fp8", "_ring": 1},
 }
 
 
@@ -130,8 +138,9 @@ def main():
     from django_assistant_bot_amd.engine.llm_engine import LLMEngine, SamplingParams
 
     torch.manual_seed(0)
+    w8 = any(ARMS[a].get("_w") == "fp8" for a in args.arms.split(","))
     eng = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=120, max_prefill_tokens=32768,
-                    block_size=args.block_size)
+                    block_size=args.block_size, weight_dtype="fp8" if w8 else "bf16")
     eng.model.__class__ = tuned_model_class()  # same object, overridable stream choice
     g = torch.Generator().manual_seed(1)
     sp = SamplingParams(max_new_tokens=6000, ignore_eos=True)
@@ -157,6 +166,7 @@ def main():
 
     base_part, base_spart = eng.long_part_size, eng.part_size
     base_groups = dict(eng.model.proj_group)
+    base_ring = ops.native().stream_gemm_fp8_deep()
     arms = args.arms.split(",")
     res = {a: [] for a in arms}
     for r in range(args.rounds):
@@ -179,6 +189,8 @@ def main():
             eng.model.l3_warm_blocks = spec.get("_warm_blocks", type(eng.model).l3_warm_blocks)
             eng.model.STREAM_CFG_RES16 = spec.get("_res_cfg", type(eng.model).STREAM_CFG_RES16)
             ops.native().stream_gemm_set_slice_xcd(spec.get("_slice_xcd", 0))
+            eng.model.fp8_stream = spec.get("_w") == "fp8"
+            ops.native().stream_gemm_fp8_set_deep(spec.get("_ring", base_ring))
             eng.model.slab_bf16 = spec.get("_slab16", type(eng.model).slab_bf16)
             for n, g in {**base_groups, **spec.get("_groups", {})}.items():
                 eng.model.set_proj_group(n, g)

@@ -134,6 +134,63 @@ def stream_sweep(which, Ms=(128,)):
             del ws
 
 
+def stream_fp8_sweep(Ms=(1, 16, 64, 128, 256), rounds=3):
+    """FP8 weights (W8A16) against bf16 on the streaming decode GEMM: the four Llama-3-8B projections
+    at decode batch M, each at the configuration, K-slices, output form and weight group the decoder
+    dispatches (qkv / o / down: bf16 split-K slabs, gate_up: SwiGLU8 on the grouped copy), cold
+    weights (a rotation of copies, > 1.25 GB per arm).  Arms: the bf16 kernel on the dequantised
+    weights, the FP8 arm with the bf16 configuration's ring depth (``fp8``) and with twice that
+    (``fp8_deep``); the arms alternate round by round, graph-timed, the median round is reported with
+    the rounds' min / max.  TB/s counts the weight bytes each arm streams."""
+    from django_assistant_bot_amd.models.llama import LlamaModel
+
+    nat = ops.native()
+    shapes = (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    for M in Ms:
+        for name, N, K in shapes:
+            cfg = LlamaModel._stream_cfg(LlamaModel, name, M, N)
+            if cfg < 0 or not nat.stream_gemm_fp8_ok(cfg):
+                emit(op=f"stream-fp8-{name}", M=M, cfg=cfg, note="not streamed / no FP8 arm at this batch")
+                continue
+            S = 1 if name == "gate_up" else LlamaModel._stream_splits(N, K, nat.stream_gemm_bn(cfg))
+            grp = LlamaModel.PROJ_GROUPS.get(name, 1)
+            epi = ops.EPI_SWIGLU8 if name == "gate_up" else ops.EPI_NONE
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            ncopy = max(2, int(2.5e9 // (N * K * 2)) + 1)
+            w16, w8 = [], []
+            for _ in range(ncopy):
+                data, exps = ops.weight_quantize_fp8((torch.randn(N, K, device="cuda") * 0.02).to(torch.bfloat16))
+                w16.append(ops.shuffle_weights(ops.weight_dequantize_fp8(data, exps), grp))
+                w8.append((ops.shuffle_weights_fp8(data, grp), exps))
+            out = (torch.empty((S, M, N), dtype=torch.bfloat16, device="cuda") if S > 1 else
+                   torch.empty((M, N // 2 if epi else N), dtype=torch.bfloat16, device="cuda"))
+            kw = dict(splits=S, epilogue=epi, out=out, nt=True, cfg=cfg, w_group=grp, slab_dtype=torch.bfloat16)
+
+            def run_fp8(deep):
+                nat.stream_gemm_fp8_set_deep(deep)  # (read at launch: baked into the captured graph)
+                return graph_time([lambda w=w, e=e: ops.stream_gemm(a, w, w_exps=e, **kw) for w, e in w8])
+
+            arms = {"bf16": lambda: graph_time([lambda w=w: ops.stream_gemm(a, w, **kw) for w in w16]),
+                    "fp8": lambda: run_fp8(0), "fp8_deep": lambda: run_fp8(1)}
+            times = {k: [] for k in arms}
+            deep0 = nat.stream_gemm_fp8_deep()
+            for _ in range(rounds):
+                for k, fn in arms.items():
+                    times[k].append(fn())
+            nat.stream_gemm_fp8_set_deep(deep0)
+            res = {"op": f"stream-fp8-{name}", "M": M, "N": N, "K": K, "cfg": cfg, "S": S, "group": grp,
+                   "nwin": nat.stream_gemm_fp8_nwin(cfg) // (2 if deep0 else 1)}
+            for k, byts in (("bf16", 2 * N * K), ("fp8", N * K + N), ("fp8_deep", N * K + N)):
+                t = sorted(times[k])[len(times[k]) // 2]
+                res[f"{k}_us"] = round(t * 1e6, 1)
+                res[f"{k}_tbps"] = round(byts / t / 1e12, 2)
+                res[f"{k}_us_min_max"] = [round(min(times[k]) * 1e6, 1), round(max(times[k]) * 1e6, 1)]
+            res["fp8_vs_bf16"] = round(res["fp8_us"] / res["bf16_us"], 3)
+            res["fp8_deep_vs_bf16"] = round(res["fp8_deep_us"] / res["bf16_us"], 3)
+            emit(**res)
+            del w16, w8
+
+
 def attn_suite():
     # prefill: 16 sequences x 1024 tokens, Llama-3-8B heads
     B, T, Hq, Hkv, D, bs = 16, 1024, 32, 8, 128, 64
@@ -402,6 +459,8 @@ if __name__ == "__main__":
     if which == "stream":
         stream_sweep(sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "all" else None,
                      tuple(int(m) for m in sys.argv[3].split(",")) if len(sys.argv) > 3 else (128,))
+    if which == "stream_fp8":
+        stream_fp8_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (1, 16, 64, 128, 256))
     if which == "decode":
         decode_sweep()
     if which in ("decode", "decodefp8"):

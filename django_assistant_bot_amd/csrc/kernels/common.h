@@ -116,6 +116,21 @@ __device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// FP8 storage (KV cache rows, weight rows): OCP e4m3fn bytes and one E8M0 exponent byte b per row,
+// value = byte x 2^(b - 127).
+// two e4m3fn bytes (the low / high half of `w`) -> two bf16, exact (4 significant bits)
+template <bool HI>
+__device__ __forceinline__ uint32_t fp8x2_bf16(uint32_t w) {
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+}
+
+__device__ __forceinline__ bf16x8 fp8x8_bf16(uint32_t lo, uint32_t hi) {
+  const u32x4 r = {fp8x2_bf16<false>(lo), fp8x2_bf16<true>(lo), fp8x2_bf16<false>(hi), fp8x2_bf16<true>(hi)};
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+__device__ __forceinline__ float exp_scale(uint32_t b) { return __uint_as_float(b << 23); }  // 2^(b - 127)
+
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 // ds_read_b64_tr_b16: per 16-lane group, lane 4q+p supplies the address of row q, columns 4p..4p+3

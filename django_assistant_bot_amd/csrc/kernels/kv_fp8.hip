@@ -19,18 +19,7 @@ namespace {
 
 constexpr float kNegInfF = -__builtin_huge_valf();
 
-// two e4m3fn bytes (the low / high half of `w`) -> two bf16, exact (4 significant bits)
-template <bool HI>
-__device__ __forceinline__ uint32_t fp8x2_bf16(uint32_t w) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-}
-
-__device__ __forceinline__ bf16x8 fp8x8_bf16(uint32_t lo, uint32_t hi) {
-  const u32x4 r = {fp8x2_bf16<false>(lo), fp8x2_bf16<true>(lo), fp8x2_bf16<false>(hi), fp8x2_bf16<true>(hi)};
-  return __builtin_bit_cast(bf16x8, r);
-}
-
-__device__ __forceinline__ float exp_scale(uint32_t b) { return __uint_as_float(b << 23); }  // 2^(b - 127)
+// (fp8x8_bf16 / exp_scale: common.h, shared with the FP8-weight decode GEMM)
 
 // Exponent byte of a row whose largest |bf16 bits| is `a` (sign cleared): amax = 1.M x 2^(E - 127),
 // the smallest power of two 2^e with amax / 2^e <= 448 is e = E - 135, or E - 134 when 1.M > 1.75.

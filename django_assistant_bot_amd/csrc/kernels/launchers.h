@@ -112,6 +112,17 @@ int stream_gemm(const void* X, long ldx, const void* W, long ldw, void* out, lon
                 int M, int N, int K, int S, int epilogue, hipStream_t s, int nt_weights, int cfg, float norm_eps = 0.f,
                 int slab_bf16 = 0, int w_group = 1);
 int stream_gemm_bn(int cfg);
+// ... with FP8 weights (W8A16): W = e4m3fn bytes in the ops.shuffle_weights_fp8 layout, w_exps = one
+// E8M0 exponent byte per weight row [N].  The same numbers as stream_gemm on the dequantised weights.
+// K % 64, a null w_exps or a cfg without an FP8 instantiation (stream_gemm_fp8_ok) -> hipErrorInvalidValue
+int stream_gemm_fp8(const void* X, long ldx, const void* W, const void* w_exps, void* out, long ldo,
+                    const void* residual, long ldr, int M, int N, int K, int S, int epilogue, hipStream_t s,
+                    int nt_weights, int cfg, float norm_eps = 0.f, int slab_bf16 = 0, int w_group = 1);
+int stream_gemm_fp8_ok(int cfg);    // 1: cfg has an FP8-weight instantiation
+int stream_gemm_fp8_nwin(int cfg);  // weight-ring stages of cfg's FP8 arm at the current ring mode (0: none)
+// FP8 arm ring depth: 0 = the bf16 configuration's, 1 = twice that (the same ring registers); A/B switch
+void stream_gemm_fp8_set_deep(int on);
+int stream_gemm_fp8_deep();
 // fp32 (or bf16: slab_bf16) split-K slabs [S][M][N] -> bf16 [M, N] (+ residual)
 int slab_reduce(void* out, long ldo, const void* slabs, int S, int M, int N, const void* residual, long ldr,
                 hipStream_t s, int slab_bf16 = 0);

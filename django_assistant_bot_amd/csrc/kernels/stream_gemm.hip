@@ -64,6 +64,11 @@ struct StreamParams {
   int cap;
 };
 
+// FP8-weight arm (its own kernel argument type: the bf16 kernels keep theirs)
+struct StreamParams8 : StreamParams {
+  const uint8_t* w_exps;  // one E8M0 exponent byte per weight row [N] (W = e4m3fn bytes)
+};
+
 constexpr int ST_EPI_NONE = 0, ST_EPI_SWIGLU = 2, ST_EPI_SWIGLU8 = 4, ST_EPI_CAND = 8;
 
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
@@ -95,8 +100,18 @@ __device__ __forceinline__ bool static_for(F&& f) {
 // NWC compute waves (waves NWC.. are the NL X loaders).  BN = 16 RT NWC / KG need not be a power of
 // two: 112 rows (7 waves) tile Llama-3-8B's 28672 gate_up rows onto exactly 256 workgroups, 96 rows
 // (6 waves, 4 K-slices) its 6144 qkv rows; the epilogue tile keeps a power-of-two row stride BNP.
-template <int MT, int RT, int KG, int KS, int NB, int NWIN, int NL, bool SHUF, bool NT_W, int ABL = 0, int NWC = 4>
-__global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamParams p) {
+//
+// W8 (FP8 weights, W8A16): W is the shuffle_weights_fp8 copy [N/16][K/64][64 lanes][16 B] of e4m3fn
+// bytes (lane l = row l & 15; bytes 0-7 k 64j + 8(l>>4).., bytes 8-15 k 64j + 32 + 8(l>>4)..), so one
+// 16-B lane load (still a 1 KB wave read) feeds two 32-deep MFMA chunks: a ring slot holds half the
+// registers.  Each half is converted to bf16 in registers (exact) right before its MFMAs; the rows'
+// power-of-two exponents multiply the fp32 sums once, in tile4.  Every dequantised weight is
+// bf16-exact and a power of two commutes with every rounding, so the result equals, bit for bit,
+// the bf16 kernel's on the dequantised weights (same operand and summation order).
+template <int MT, int RT, int KG, int KS, int NB, int NWIN, int NL, bool SHUF, bool NT_W, int ABL = 0, int NWC = 4,
+          bool W8 = false>
+__global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
+    std::conditional_t<W8, StreamParams8, StreamParams> p) {
   constexpr int RG = NWC / KG;        // row groups
   constexpr int BN = 16 * RT * RG;    // weight rows per workgroup
   constexpr int BNP = BN <= 64 ? 64 : BN <= 128 ? 128 : 256;  // epilogue tile row stride (XOR swizzle range)
@@ -108,6 +123,10 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamP
   constexpr int GPL = GPS / NL;       // ... per loader wave
   constexpr int KW = KS / KG;         // k per compute wave per stage
   constexpr int CPW = KW / 32;        // 32-deep MFMA chunks per wave per stage
+  constexpr int WK = W8 ? 64 : 32;            // k per 1 KB weight fragment (SHUF)
+  constexpr int EB = W8 ? 1 : 2;              // bytes per weight
+  constexpr int LPW = W8 ? CPW / 2 : CPW;     // 16-B weight loads per wave, row tile and stage
+  static_assert(!W8 || (SHUF && ABL == 0 && CPW % 2 == 0), "FP8 weights: fragment layout, whole 64-deep steps");
   constexpr int RED = KG * MP * BNP * 4;
   static_assert(BN <= 256 && BN % 16 == 0, "tile rows");
   // + per-row scales of the consumer RMSNorm and each wave's per-row sums of squares (after the ring
@@ -183,28 +202,28 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamP
     // group are adjacent per 32-deep k chunk, fragment (b, c) at ((b / G) K/32 + c) G + b % G KB;
     // block offsets are then absolute (descriptor over the whole copy) and a k chunk is G KB on
     const bool grp = SHUF && p.wgrp > 1;
-    const auto wres = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (grp ? 0 : (size_t)n0 * p.ldw)), 0,
-                                                        grp ? (int)((long)p.N * p.K * 2) : (int)(w_rows * p.ldw * 2),
-                                                        0x00020000);
-    const int cstride = SHUF ? (grp ? p.wgrp : 1) * 1024 : 0;  // bytes per 32-deep k chunk (SHUF)
+    const auto wres = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)p.W + (grp ? 0 : (size_t)n0 * p.ldw * EB)), 0,
+        grp ? (int)((long)p.N * p.K * EB) : (int)(w_rows * p.ldw * EB), 0x00020000);
+    const int cstride = SHUF ? (grp ? p.wgrp : 1) * 1024 : 0;  // bytes per WK-deep k chunk (SHUF)
     // row-major W: lane (li, g) reads row li, k 8g..8g+7 of a 16 x 32 chunk (16 rows x 64 B per load);
     // SHUF (shuffle_weights layout [N/16][K/32][64 lanes][8]): every load is 1 KB contiguous
-    const int w_voff = SHUF ? lane * 16 + ((k_begin + kg * KW) / 32) * cstride
+    const int w_voff = SHUF ? lane * 16 + ((k_begin + kg * KW) / WK) * cstride
                             : (int)(((16 * RT * rg + li) * p.ldw + k_begin + kg * KW + 8 * g) * 2);
-    const int a_stride = SHUF ? p.K * 32 : 16 * (int)p.ldw * 2;
-    const int w_rowtile0 = SHUF ? RT * rg * p.K * 32 : 0;
+    const int a_stride = SHUF ? p.K * 16 * EB : 16 * (int)p.ldw * 2;
+    const int w_rowtile0 = SHUF ? RT * rg * p.K * 16 * EB : 0;
     // SHUF: byte offset of row block (RT rg + a) of the tile at k chunk 0
     int wblk[RT];
 #pragma unroll
     for (int a = 0; a < RT; ++a) {
       if (grp) {
         const int b = n0 / 16 + RT * rg + a;
-        wblk[a] = ((b / p.wgrp) * (p.K / 32) * p.wgrp + b % p.wgrp) * 1024;
+        wblk[a] = ((b / p.wgrp) * (p.K / WK) * p.wgrp + b % p.wgrp) * 1024;
       } else {
         wblk[a] = a * a_stride + w_rowtile0;
       }
     }
-    bf16x8 wr[NWIN][RT][CPW];
+    bf16x8 wr[NWIN][RT][LPW];  // (W8: 16 e4m3fn bytes, two chunks)
     // clamped past the slice end: the ring keeps a branch-free load stream, so the compiler's
     // in-order vmcnt count stays exact (the spare loads re-read the last stage from L2)
     auto load_w = [&](int slot, int st, int a, int c) DAB_INLINE {
@@ -216,7 +235,7 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamP
         const int off = (chunk * (BN / 16) + RT * rg + a) * 1024 + lane * 16;
         wr[slot][a][c] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wres, off, 0, NT_W ? 2 : 0));
       } else if constexpr (SHUF) {
-        const int soff = min(st, nst - 1) * (KS / 32) * cstride + wblk[a];
+        const int soff = min(st, nst - 1) * (KS / WK) * cstride + wblk[a];
         wr[slot][a][c] = __builtin_bit_cast(
             bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wres, w_voff + cstride * c, soff, NT_W ? 2 : 0));
       } else {
@@ -230,7 +249,7 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamP
 #pragma unroll
       for (int a = 0; a < RT; ++a)
 #pragma unroll
-        for (int c = 0; c < CPW; ++c) load_w(s, s, a, c);
+        for (int c = 0; c < LPW; ++c) load_w(s, s, a, c);
       return true;
     });
     f32x4 acc[RT][MT];
@@ -257,11 +276,19 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamP
 #pragma unroll
               for (int t = 0; t < MT; ++t) asm volatile("" ::"v"(bx[t]));
             }
+          } else if constexpr (W8) {
+            const u32x4 b8 = __builtin_bit_cast(u32x4, wr[h][a][c / 2]);
+            const bf16x8 wa = (c & 1) ? fp8x8_bf16(b8[2], b8[3]) : fp8x8_bf16(b8[0], b8[1]);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wa, bx[t], acc[a][t]);
           } else {
 #pragma unroll
             for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wr[h][a][c], bx[t], acc[a][t]);
           }
-          load_w(h, st + NWIN, a, c);
+          if constexpr (!W8)
+            load_w(h, st + NWIN, a, c);
+          else if (c & 1)  // (unrolled: static) both halves of the 16 bytes are consumed
+            load_w(h, st + NWIN, a, c / 2);
           // keep the reload right behind its MFMAs (the scheduler would otherwise sink every
           // reload to the stage end and halve the bytes in flight)
           __builtin_amdgcn_sched_barrier(0);
@@ -333,6 +360,10 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(StreamP
     f32x4 v = *reinterpret_cast<const f32x4*>(red + m * BNP + col);
 #pragma unroll
     for (int q = 1; q < KG; ++q) v += *reinterpret_cast<const f32x4*>(red + (q * MP + m) * BNP + col);
+    if constexpr (W8) {  // the 4 weight rows' exponents, on the fp32 sums
+      const uint32_t eb = *reinterpret_cast<const uint32_t*>(p.w_exps + n0 + c4);
+      v *= f32x4{exp_scale(eb & 0xff), exp_scale((eb >> 8) & 0xff), exp_scale((eb >> 16) & 0xff), exp_scale(eb >> 24)};
+    }
     if (p.norm) v *= rsq[m];
     return v;
   };
@@ -508,6 +539,36 @@ static void launch_cfg(const StreamParams& p, hipStream_t s, bool nt) {
                        block, 0, s, p);
 }
 
+// FP8-weight instantiations: the configurations the decoder dispatches for qkv / o / gate_up / down
+// (LlamaModel._stream_cfg, STREAM_WIDE["gate_up"], STREAM_CFG_RES16).  DEEP: twice the weight-ring
+// stages of the bf16 configuration, i.e. the same ring registers and bytes in flight.
+constexpr bool fp8_cfg(int c) { return c == 10 || c == 13 || c == 20 || c == 27 || c == 30 || c == 31 || c == 32; }
+
+template <int C, bool DEEP>
+static void launch_cfg_fp8(const StreamParams8& p, hipStream_t s, bool nt) {
+  constexpr StreamCfg c = kStreamCfgs[C];
+  constexpr int nwin = c.nwin * (DEEP ? 2 : 1);
+  const int bn = 16 * c.rt * (c.nwc / c.kg);
+  const dim3 grid((p.N / bn) * p.S), block(64 * (c.nwc + c.nl));
+  if (nt)
+    hipLaunchKernelGGL((stream_gemm_kernel<c.mt, c.rt, c.kg, 128, c.nb, nwin, c.nl, true, true, 0, c.nwc, true>), grid,
+                       block, 0, s, p);
+  else
+    hipLaunchKernelGGL((stream_gemm_kernel<c.mt, c.rt, c.kg, 128, c.nb, nwin, c.nl, true, false, 0, c.nwc, true>), grid,
+                       block, 0, s, p);
+}
+
+template <int C = 0>
+static void launch_any_fp8(int cfg, const StreamParams8& p, hipStream_t s, bool nt, bool deep) {
+  if constexpr (C < kNumStreamCfgs) {
+    if constexpr (fp8_cfg(C)) {
+      static_assert(kStreamCfgs[C].shuf && kStreamCfgs[C].abl == 0, "FP8 arm: fragment-layout configurations");
+      if (cfg == C) return deep ? launch_cfg_fp8<C, true>(p, s, nt) : launch_cfg_fp8<C, false>(p, s, nt);
+    }
+    launch_any_fp8<C + 1>(cfg, p, s, nt, deep);
+  }
+}
+
 int stream_gemm_bn(int cfg) {
   if (cfg < 0 || cfg >= kNumStreamCfgs) return 0;
   return 16 * kStreamCfgs[cfg].rt * (kStreamCfgs[cfg].nwc / kStreamCfgs[cfg].kg);
@@ -533,9 +594,20 @@ static int g_slice_xcd = [] {
 void stream_gemm_set_slice_xcd(int on) { g_slice_xcd = on; }
 int stream_gemm_slice_xcd() { return g_slice_xcd; }
 
-int stream_gemm(const void* X, long ldx, const void* W, long ldw, void* out, long ldo, const void* residual, long ldr,
-                int M, int N, int K, int S, int epilogue, hipStream_t s, int nt_weights, int cfg, float norm_eps,
-                int slab_bf16, int w_group) {
+// FP8 arm ring depth (A/B; DAB_STREAM_FP8_DEEP): see launch_cfg_fp8
+static int g_fp8_deep = [] {
+  const char* e = std::getenv("DAB_STREAM_FP8_DEEP");
+  return e ? std::atoi(e) != 0 : 0;
+}();
+void stream_gemm_fp8_set_deep(int on) { g_fp8_deep = on != 0; }
+int stream_gemm_fp8_deep() { return g_fp8_deep; }
+int stream_gemm_fp8_ok(int cfg) { return cfg >= 0 && cfg < kNumStreamCfgs && fp8_cfg(cfg); }
+int stream_gemm_fp8_nwin(int cfg) { return stream_gemm_fp8_ok(cfg) ? kStreamCfgs[cfg].nwin * (g_fp8_deep ? 2 : 1) : 0; }
+
+// w_exps == nullptr: bf16 weights (row stride ldw); else the FP8 fragment copy + row exponents
+static int stream_gemm_any(const void* X, long ldx, const void* W, long ldw, const uint8_t* w_exps, void* out, long ldo,
+                           const void* residual, long ldr, int M, int N, int K, int S, int epilogue, hipStream_t s,
+                           int nt_weights, int cfg, float norm_eps, int slab_bf16, int w_group) {
   constexpr int KS = 128;
   if (M <= 0 || N <= 0) return 0;
   const int bn = stream_gemm_bn(cfg);
@@ -545,7 +617,8 @@ int stream_gemm(const void* X, long ldx, const void* W, long ldw, void* out, lon
   if (epilogue == ST_EPI_SWIGLU && bn % 32) return hipErrorInvalidValue;  // whole 16 + 16 row pairs per tile
   if (S > 1 && (epilogue != ST_EPI_NONE || residual)) return hipErrorInvalidValue;
   if (residual && ldr % 8) return hipErrorInvalidValue;
-  if ((long)bn * ldw * 2 >= (1L << 31)) return hipErrorInvalidValue;  // buffer descriptor range
+  const long eb = w_exps ? 1 : 2;  // bytes per weight
+  if ((long)bn * ldw * eb >= (1L << 31)) return hipErrorInvalidValue;  // buffer descriptor range
   if (kStreamCfgs[cfg].shuf && (ldw != K || K % 32)) return hipErrorInvalidValue;
   StreamParams p{};
   p.X = (const bf16*)X;
@@ -569,11 +642,30 @@ int stream_gemm(const void* X, long ldx, const void* W, long ldw, void* out, lon
   p.slice_xcd = g_slice_xcd && S % 8 == 0;
   p.slab_bf16 = S > 1 && slab_bf16;
   p.wgrp = w_group < 1 ? 1 : w_group;
-  if (p.wgrp > 1 && (!kStreamCfgs[cfg].shuf || N % (16 * p.wgrp) || (long)N * K * 2 >= (1L << 31)))
+  if (p.wgrp > 1 && (!kStreamCfgs[cfg].shuf || N % (16 * p.wgrp) || (long)N * K * eb >= (1L << 31)))
     return hipErrorInvalidValue;
   if (p.norm && (residual || K % 8 || M > stream_gemm_max_m(cfg))) return hipErrorInvalidValue;
-  launch_any(cfg, p, s, nt_weights != 0);
+  if (w_exps)
+    launch_any_fp8(cfg, StreamParams8{p, w_exps}, s, nt_weights != 0, g_fp8_deep != 0);
+  else
+    launch_any(cfg, p, s, nt_weights != 0);
   return hipGetLastError();
+}
+
+int stream_gemm(const void* X, long ldx, const void* W, long ldw, void* out, long ldo, const void* residual, long ldr,
+                int M, int N, int K, int S, int epilogue, hipStream_t s, int nt_weights, int cfg, float norm_eps,
+                int slab_bf16, int w_group) {
+  return stream_gemm_any(X, ldx, W, ldw, nullptr, out, ldo, residual, ldr, M, N, K, S, epilogue, s, nt_weights, cfg,
+                         norm_eps, slab_bf16, w_group);
+}
+
+int stream_gemm_fp8(const void* X, long ldx, const void* W, const void* w_exps, void* out, long ldo,
+                    const void* residual, long ldr, int M, int N, int K, int S, int epilogue, hipStream_t s,
+                    int nt_weights, int cfg, float norm_eps, int slab_bf16, int w_group) {
+  // (the exponents are read 4 rows at a time)
+  if (K % 64 || !w_exps || (uintptr_t)w_exps % 4 || !stream_gemm_fp8_ok(cfg)) return hipErrorInvalidValue;
+  return stream_gemm_any(X, ldx, W, K, (const uint8_t*)w_exps, out, ldo, residual, ldr, M, N, K, S, epilogue, s,
+                         nt_weights, cfg, norm_eps, slab_bf16, w_group);
 }
 
 // Sum S fp32 / bf16 slabs -> bf16 (optionally + residual), rounded like a bf16 GEMM output before the

@@ -104,7 +104,8 @@ class LLMEngine:
                  tp_group=None, tp_size: int = 1, tp_rank: int = 0, interleaved_mlp: bool = True,
                  part_size: int = 512, kv_memory_fraction: float = 0.85, mixed_prefill_tokens: int = 0,
                  pipeline_decode: bool = True, shared_model: LlamaModel | None = None,
-                 kv_cache_dtype: str | None = None, kv_scratch_blocks: int | None = None):
+                 kv_cache_dtype: str | None = None, kv_scratch_blocks: int | None = None,
+                 weight_dtype: str | None = None):
         """``shared_model``: serve with another engine's ``LlamaModel`` (one copy of the weights, a
         KV pool / scheduler / HIP graphs of this engine's own; e.g. two engines on two streams whose
         prefill and decode phases overlap: bench.py --mode overlap).
@@ -112,9 +113,26 @@ class LLMEngine:
         ``kv_cache_dtype``: ``"bf16"`` or ``"fp8"`` (opt-in FP8 KV cache: docs/ARCHITECTURE.md); ``None``
         reads ``DAB_KV_CACHE_DTYPE`` from the environment, else bf16.  ``kv_scratch_blocks``: size of
         the FP8 cache's bf16 prefill scratch (default: ``max(max_prefill_tokens, max_model_len) /
-        block_size + max_batch`` blocks)."""
+        block_size + max_batch`` blocks).
+
+        ``weight_dtype``: ``"bf16"`` or ``"fp8"`` (opt-in FP8 projection weights for the streaming
+        decode GEMM, ``LlamaModel(weight_dtype=...)``: docs/ARCHITECTURE.md "FP8 weights"); ``None``
+        reads ``DAB_WEIGHT_DTYPE`` from the environment, else bf16.  With ``shared_model`` the engine
+        adopts the model's; a conflicting argument raises."""
         self.cfg = decoder_config(model) if isinstance(model, str) else model
         cfg = self.cfg
+        if shared_model is not None:
+            have = getattr(shared_model, "weight_dtype", "bf16")
+            if weight_dtype is not None and weight_dtype != have:
+                raise ValueError(f"weight_dtype={weight_dtype!r} conflicts with the shared model's {have!r}")
+            weight_dtype = have
+        elif weight_dtype is None:
+            weight_dtype = os.environ.get("DAB_WEIGHT_DTYPE") or "bf16"
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        if weight_dtype == "fp8" and tp_size > 1:
+            raise ValueError("weight_dtype='fp8' does not support tensor parallelism (tp_size > 1) yet")
+        self.weight_dtype = weight_dtype
         if kv_cache_dtype is None:
             kv_cache_dtype = os.environ.get("DAB_KV_CACHE_DTYPE") or "bf16"
         if kv_cache_dtype not in ("bf16", "fp8"):
@@ -147,7 +165,8 @@ class LLMEngine:
             self.model = shared_model
         else:
             self.model = LlamaModel(cfg, weights, self.device, tp_group=tp_group, tp_size=tp_size,
-                                    interleaved_mlp=interleaved_mlp, consume=own_weights, tp_rank=tp_rank)
+                                    interleaved_mlp=interleaved_mlp, consume=own_weights, tp_rank=tp_rank,
+                                    weight_dtype=weight_dtype)
         del weights
         if self.is_gpu and shared_model is None:
             # the caller's weight dict held the row-major originals while the model converted them
@@ -204,7 +223,9 @@ class LLMEngine:
                       "preemptions": 0, "graph_replays": 0, "mixed_steps": 0,
                       # the KV cache's element width (16: bf16, 8: fp8 = ``kv_cache_dtype``); a number like
                       # every other entry, since consumers subtract two snapshots of this dict
-                      "kv_cache_bits": 8 if fp8 else 16}
+                      "kv_cache_bits": 8 if fp8 else 16,
+                      # the projection weights the decode GEMM streams (8: ``weight_dtype="fp8"``)
+                      "weight_bits": 8 if weight_dtype == "fp8" else 16}
         # decode static buffers (graph inputs / outputs)
         self.use_graphs = use_graphs and self.is_gpu
         dev = self.device

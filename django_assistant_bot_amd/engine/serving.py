@@ -230,6 +230,7 @@ def get_llm_worker(model: str, **engine_kwargs) -> LLMWorker:
             engine_kwargs.setdefault("block_size", setting("KV_BLOCK_SIZE", 64))
             engine_kwargs.setdefault("max_prefill_tokens", setting("MAX_BATCH_TOKENS", 65536))
             engine_kwargs.setdefault("kv_cache_dtype", setting("KV_CACHE_DTYPE", None))  # None: env, else bf16
+            engine_kwargs.setdefault("weight_dtype", setting("WEIGHT_DTYPE", None))  # (likewise)
             if engine_kwargs["device"] == "cpu":
                 engine_kwargs.setdefault("max_model_len", 2048)
             w = _llm[key] = LLMWorker(LLMEngine(model, **engine_kwargs))

@@ -28,7 +28,8 @@ from .configs import DecoderConfig
 class DecoderLayer:
     """One layer's tensors.  On the GPU the four projections are held ONCE, in the
     ``ops.shuffle_weights`` fragment layout, which the decode GEMM (stream_gemm) streams and the
-    prefill GEMMs (gemm256 / gemm_bt ``shuffled``) stage by LDS-DMA; on the CPU they are row-major."""
+    prefill GEMMs (gemm256 / gemm_bt ``shuffled``) stage by LDS-DMA; on the CPU they are row-major.
+    Under ``weight_dtype="fp8"`` (GPU, fragment layout) each projection is an ``Fp8Proj``."""
 
     attn_norm: torch.Tensor
     qkv_w: torch.Tensor
@@ -36,6 +37,41 @@ class DecoderLayer:
     mlp_norm: torch.Tensor
     gate_up_w: torch.Tensor  # [gate 8 | up 8] row groups (interleaved) or [gate; up] (stacked)
     down_w: torch.Tensor
+
+
+class Fp8Proj:
+    """One projection of a ``weight_dtype="fp8"`` decoder on the GPU, held twice: ``data`` / ``exps``,
+    the e4m3fn bytes in the ``ops.shuffle_weights_fp8`` layout and one power-of-two exponent byte per
+    output row, streamed by the decode GEMM (stream_gemm's FP8 arm), and ``w``, a bf16
+    ``ops.shuffle_weights`` copy of the DEQUANTISED values for the MFMA GEMMs (gemm256 / gemm_mid /
+    gemm_bt).  Both hold the same numbers, so prefill, mixed steps and every decode batch compute
+    with identical weights.  ``group``: the row-block group of both copies."""
+
+    __slots__ = ("w", "data", "exps", "group")
+
+    def __init__(self, w: torch.Tensor, data: torch.Tensor, exps: torch.Tensor, group: int = 1):
+        self.w, self.data, self.exps, self.group = w, data, exps, group
+
+    @classmethod
+    def from_rows(cls, data: torch.Tensor, exps: torch.Tensor, group: int = 1) -> "Fp8Proj":
+        """From row-major e4m3fn bytes [N, K] and row exponents [N] (``ops.weight_quantize_fp8``)."""
+        return cls(ops.shuffle_weights(ops.weight_dequantize_fp8(data, exps), group),
+                   ops.shuffle_weights_fp8(data, group), exps.contiguous(), group)
+
+    @property
+    def shape(self):
+        return self.w.shape
+
+    def regroup(self, group: int) -> None:
+        """Re-lay both copies for ``group``, in place (pointers stay valid)."""
+        self.w.copy_(ops.shuffle_weights(ops.unshuffle_weights(self.w, self.group), group))
+        self.data.copy_(ops.shuffle_weights_fp8(ops.unshuffle_weights_fp8(self.data, self.group), group))
+        self.group = group
+
+
+def _bf16_copy(w):
+    """The bf16 tensor of a projection (a tensor, or an ``Fp8Proj``'s dequantised copy)."""
+    return w.w if isinstance(w, Fp8Proj) else w
 
 
 @dataclass
@@ -164,8 +200,18 @@ class LlamaModel:
 
     def __init__(self, cfg: DecoderConfig, weights: dict, device, tp_group=None, tp_size: int = 1,
                  interleaved_mlp: bool = False, fragment_layout: bool = True, consume: bool = False,
-                 tp_rank: int | None = None, vocab_parallel: bool = True, small_norm_fused: bool | None = None):
-        """``consume``: the entries of ``weights`` are popped as the model takes them over, so each
+                 tp_rank: int | None = None, vocab_parallel: bool = True, small_norm_fused: bool | None = None,
+                 weight_dtype: str = "bf16"):
+        """``weight_dtype="fp8"`` (opt-in, TP 1): the qkv / o / gate_up / down weights are quantised at
+        load time to e4m3fn bytes with one power-of-two exponent per output row
+        (``ops.weight_quantize_fp8``) and the model computes with the dequantised values everywhere.
+        On the GPU with the fragment layout each projection is an ``Fp8Proj``: the decode GEMM
+        streams the FP8 bytes (half the weight traffic of a decode step), the prefill GEMMs read a
+        bf16 copy of the same values.  A bandwidth feature, not a capacity one: the projections take
+        1.5x the bf16 model's memory.  Embedding, norms and LM head stay bf16.  On the CPU (or
+        without the fragment layout) the weights are the dequantised row-major tensors.
+
+        ``consume``: the entries of ``weights`` are popped as the model takes them over, so each
         original is freed as soon as its fragment-layout copy exists (peak HBM = model + one
         tensor: 70B at TP 1 needs it, 2 x 140 GB would not fit in 288 GB).
 
@@ -175,6 +221,11 @@ class LlamaModel:
         samples from the all-gathered per-slice candidates (``ops.sample_candidates`` /
         ``sample_merge``).  Needs V % (32 tp) == 0 (whole JSON-mask words per slice); otherwise the
         head stays replicated."""
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        if weight_dtype == "fp8" and tp_size > 1:
+            raise ValueError("weight_dtype='fp8' is not supported under tensor parallelism (tp_size > 1)")
+        self.weight_dtype = weight_dtype
         self.cfg = cfg
         self.device = torch.device(device)
         if tp_rank is None:
@@ -208,11 +259,16 @@ class LlamaModel:
         def fmt(name, t):
             """The decoder's one copy of projection ``name``: the fragment layout, grouped per
             ``PROJ_GROUPS`` where the shape allows (layer 0 decides for every layer)."""
+            fp8 = self.weight_dtype == "fp8"
+            if fp8:
+                data, exps = ops.weight_quantize_fp8(t)
             if not self.frag:
-                return t
+                return ops.weight_dequantize_fp8(data, exps).to(t.dtype) if fp8 else t
             if name not in self.proj_group:
                 g = self.PROJ_GROUPS.get(name, 1)
                 self.proj_group[name] = g if (t.shape[0] % (16 * g) == 0 and t.numel() * 2 < (1 << 31)) else 1
+            if fp8:
+                return Fp8Proj.from_rows(data, exps, self.proj_group[name])
             return ops.shuffle_weights(t, self.proj_group[name])
 
         self.embed = take("embed").to(self.device)
@@ -291,7 +347,10 @@ class LlamaModel:
             w = getattr(L, name + "_w")
             if w.shape[0] % (16 * group):
                 raise ValueError(f"{name}: {w.shape[0]} rows are not whole groups of {group}")
-            w.copy_(ops.shuffle_weights(ops.unshuffle_weights(w, old), group))
+            if isinstance(w, Fp8Proj):
+                w.regroup(group)
+            else:
+                w.copy_(ops.shuffle_weights(ops.unshuffle_weights(w, old), group))
         self.proj_group[name] = group
 
     def _fragment_ok(self, weights: dict) -> bool:
@@ -406,12 +465,27 @@ class LlamaModel:
         if dec and self.frag:
             cfg, s = self._stream_choice(name, x.shape[0], w.shape[0], w.shape[1])
             if cfg >= 0:
+                sw, e = self._stream_w(w, name, cfg)
                 if epilogue != ops.EPI_NONE:
-                    return ops.stream_gemm(x, w, epilogue=epilogue, nt=True, cfg=cfg, w_group=grp)
+                    return ops.stream_gemm(x, sw, epilogue=epilogue, nt=True, cfg=cfg, w_group=grp, w_exps=e)
                 sd = torch.bfloat16 if (self.slab_bf16 and self.tp_size == 1 and not slab_f32) else torch.float32
-                out = ops.stream_gemm(x, w, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp)
+                out = ops.stream_gemm(x, sw, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp, w_exps=e)
                 return ops.slab_reduce(out) if (s > 1 and not allow_slabs) else out
-        return ops.gemm_bt(x, w, epilogue=epilogue, shuffled=self.frag, b_group=grp)
+        return ops.gemm_bt(x, _bf16_copy(w), epilogue=epilogue, shuffled=self.frag, b_group=grp)
+
+    # FP8 weights: (projection, stream_gemm cfg) pairs that stream the bf16 copy although the cfg has
+    # an FP8 instantiation: the per-shape opt-out for ranges that measure slower (profiles/weight_fp8.md)
+    FP8_STREAM_OFF: frozenset = frozenset()
+    fp8_stream = True  # off: every stream_gemm call reads the bf16 copies (benchmarks/decode_ab.py A/B)
+
+    def _stream_w(self, w, name: str, cfg: int):
+        """(weights, row exponents or None) for a stream_gemm call at ``cfg``: the FP8 copy of an
+        ``Fp8Proj`` where the kernel has an FP8 arm for ``cfg``, else the bf16 copy (same values)."""
+        if not isinstance(w, Fp8Proj):
+            return w, None
+        if self.fp8_stream and ops.native().stream_gemm_fp8_ok(cfg) and (name, cfg) not in self.FP8_STREAM_OFF:
+            return w.data, w.exps
+        return w.w, None
 
     # Pure prefill steps whose caller reads only ``out_rows`` (the last token of each finished
     # prompt, ~30 rows of 32k): everything after the LAST layer's attention is row-wise -- o + residual,
@@ -483,17 +557,18 @@ class LlamaModel:
         T = h.shape[0]
         c, s = self._stream_choice("qkv", T, L.qkv_w.shape[0], L.qkv_w.shape[1])
         pg = self.proj_group
-        qkv = ops.stream_gemm(h, L.qkv_w, splits=s, cfg=c, nt=True, norm_eps=cfg.eps, w_group=pg.get("qkv", 1))
+        R = self.STREAM_CFG_RES16
+        (qw, qe), (ow, oe) = self._stream_w(L.qkv_w, "qkv", c), self._stream_w(L.o_w, "o", R)
+        qkv = ops.stream_gemm(h, qw, splits=s, cfg=c, nt=True, norm_eps=cfg.eps, w_group=pg.get("qkv", 1), w_exps=qe)
         q = kv.write(li, qkv, meta.positions, self.cos_sin, meta.slots, self.hq, self.hkv, D)
         a = kv.decode_attention(li, q, meta.block_tables, meta.ctx_lens, meta.part_size, meta.workspace,
                                 order=meta.order)
-        h1 = ops.stream_gemm(a.view(T, self.hq * D), L.o_w, residual=h, cfg=self.STREAM_CFG_RES16, nt=True,
-                             w_group=pg.get("o", 1))
+        h1 = ops.stream_gemm(a.view(T, self.hq * D), ow, residual=h, cfg=R, nt=True, w_group=pg.get("o", 1), w_exps=oe)
         gc, _ = self._stream_choice("gate_up", T, L.gate_up_w.shape[0], L.gate_up_w.shape[1])
-        act = ops.stream_gemm(h1, L.gate_up_w, epilogue=ops.EPI_SWIGLU8, cfg=gc, nt=True, norm_eps=cfg.eps,
-                              w_group=pg.get("gate_up", 1))
-        return ops.stream_gemm(act, L.down_w, residual=h1, cfg=self.STREAM_CFG_RES16, nt=True,
-                               w_group=pg.get("down", 1))
+        (gw, ge), (dw, de) = self._stream_w(L.gate_up_w, "gate_up", gc), self._stream_w(L.down_w, "down", R)
+        act = ops.stream_gemm(h1, gw, epilogue=ops.EPI_SWIGLU8, cfg=gc, nt=True, norm_eps=cfg.eps,
+                              w_group=pg.get("gate_up", 1), w_exps=ge)
+        return ops.stream_gemm(act, dw, residual=h1, cfg=R, nt=True, w_group=pg.get("down", 1), w_exps=de)
 
     # Small decode batches: the paged attention is a chain of dependent memory round trips on a few
     # dozen CUs (~15 us per layer at batch 1 while HBM idles).  ``l3_warm_mb`` > 0 appends
@@ -507,11 +582,14 @@ class LlamaModel:
     def _warm(self, L: DecoderLayer, T: int, ref):
         if not self.l3_warm_mb or T > self.L3_WARM_MAX_M or not ref.is_cuda:
             return None
+        o_w, gu_w = L.o_w, L.gate_up_w
+        if isinstance(o_w, Fp8Proj):  # the bytes the decode GEMM streams
+            o_w, gu_w = o_w.data, gu_w.data
         budget = int(self.l3_warm_mb * 2 ** 20) & ~15
-        ob = L.o_w.numel() * L.o_w.element_size()
-        ranges = [(L.o_w, min(ob, budget))]
+        ob = o_w.numel() * o_w.element_size()
+        ranges = [(o_w, min(ob, budget))]
         if budget > ob:
-            ranges.append((L.gate_up_w, min(budget - ob, L.gate_up_w.numel() * L.gate_up_w.element_size()) & ~15))
+            ranges.append((gu_w, min(budget - ob, gu_w.numel() * gu_w.element_size()) & ~15))
         return ranges, self.l3_warm_blocks
 
     def _final_norm(self, x, residual):
@@ -591,17 +669,19 @@ class LlamaModel:
         if rows.dtype != torch.int32:
             rows = rows.to(torch.int32)
         pg = self.proj_group
-        res = ops.gemm_bt(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=True, b_group=pg.get("o", 1),
-                          rows=rows)
+        res = ops.gemm_bt(a.view(T, self.hq * D), _bf16_copy(L.o_w), residual=residual, shuffled=True,
+                          b_group=pg.get("o", 1), rows=rows)
         h, _ = ops.rmsnorm(res, L.mlp_norm, self.cfg.eps)
-        act = ops.gemm_bt(h, L.gate_up_w, epilogue=ops.EPI_SWIGLU8, shuffled=True, b_group=pg.get("gate_up", 1), as_m=T)
-        return None, ops.gemm_bt(act, L.down_w, residual=res, shuffled=True, b_group=pg.get("down", 1), as_m=T)
+        act = ops.gemm_bt(h, _bf16_copy(L.gate_up_w), epilogue=ops.EPI_SWIGLU8, shuffled=True,
+                          b_group=pg.get("gate_up", 1), as_m=T)
+        return None, ops.gemm_bt(act, _bf16_copy(L.down_w), residual=res, shuffled=True, b_group=pg.get("down", 1),
+                                 as_m=T)
 
     def _layer_tail(self, L, a, residual, sk, fuse, slabs_ok, T, D):
         """o projection, MLP norm, gate_up (+SwiGLU), down: -> (next layer input, residual stream)."""
         cfg = self.cfg
         if fuse:
-            residual = ops.gemm_bt(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=self.frag,
+            residual = ops.gemm_bt(a.view(T, self.hq * D), _bf16_copy(L.o_w), residual=residual, shuffled=self.frag,
                                    b_group=self.proj_group.get("o", 1))
             h, _ = ops.rmsnorm(residual, L.mlp_norm, cfg.eps)
         elif sk and self.tp_size > 1:
@@ -617,7 +697,7 @@ class LlamaModel:
         if h.is_cuda and epi == ops.EPI_NONE:
             act = ops.silu_mul(act)
         if fuse:
-            return None, ops.gemm_bt(act, L.down_w, residual=residual, shuffled=self.frag,
+            return None, ops.gemm_bt(act, _bf16_copy(L.down_w), residual=residual, shuffled=self.frag,
                                      b_group=self.proj_group.get("down", 1))
         if sk and self.tp_size > 1:  # reduced inside the next layer's (or the final) norm launch
             return self._tp_partial(self._proj(act, L.down_w, sk, True, name="down"), cfg.hidden), residual

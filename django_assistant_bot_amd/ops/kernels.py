@@ -896,8 +896,36 @@ def unshuffle_weights(w: torch.Tensor, group: int = 1) -> torch.Tensor:
     return w.reshape(N // 16, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).contiguous().view(N, K)
 
 
+weight_quantize_fp8 = ref.weight_quantize_fp8
+weight_dequantize_fp8 = ref.weight_dequantize_fp8
+
+
+def shuffle_weights_fp8(data: torch.Tensor, group: int = 1) -> torch.Tensor:
+    """e4m3fn bytes [N, K] (uint8, row-major) -> the FP8 fragment layout [N/16][K/64][64 lanes][16 B]
+    the streaming decode GEMM's FP8 arm reads: lane l holds row l & 15, its bytes 0-7 are
+    k = 64j + 8 (l >> 4) .. + 8 and its bytes 8-15 k = 64j + 32 + 8 (l >> 4) .. + 8, so one 16-byte lane
+    load (a fully coalesced 1 KB wave read) feeds two 32-deep MFMA chunks.  ``group`` G > 1 as in
+    ``shuffle_weights``: the fragments of G consecutive 16-row blocks adjacent per 64-deep k step.
+    Returned with shape [N, K]."""
+    N, K = data.shape
+    expect(data.dtype == torch.uint8, "shuffle_weights_fp8 takes e4m3fn bytes (uint8)")
+    expect(N % (16 * group) == 0 and K % 64 == 0, "shuffle_weights_fp8 needs N % (16 group) == 0 and K % 64 == 0")
+    f = data.reshape(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5)  # [blk, j, l >> 4, l & 15, half, 8]
+    if group > 1:
+        f = f.reshape(N // (16 * group), group, K // 64, 1024).permute(0, 2, 1, 3)
+    return f.contiguous().view(N, K)
+
+
+def unshuffle_weights_fp8(data: torch.Tensor, group: int = 1) -> torch.Tensor:
+    """Inverse of ``shuffle_weights_fp8``."""
+    N, K = data.shape
+    if group > 1:
+        data = data.reshape(N // (16 * group), K // 64, group, 1024).permute(0, 2, 1, 3)
+    return data.reshape(N // 16, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).contiguous().view(N, K)
+
+
 def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=False, cfg=0, norm_eps: float = 0.0,
-                slab_dtype=torch.float32, w_group: int = 1):
+                slab_dtype=torch.float32, w_group: int = 1, w_exps=None):
     """Decode GEMM y = x w^T on the warp-specialised streaming kernel (``stream_gemm.hip``): bf16
     [M, N] (optional residual add), SwiGLU [M, N/2] over 16- / 8-row interleaved [gate | up] rows, or
     fp32 K-slice slabs [S, M, N] (their sum is the product; consumers sum them in their prologue or
@@ -907,12 +935,28 @@ def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=F
     RMSNorm gains in its columns; the kernel scales row m by rsqrt(mean(x[m]^2) + eps) (the
     consumer-side RMSNorm of small decode batches).  ``slab_dtype`` bf16: the split-K slabs are the
     partial sums rounded to bf16 (half the bytes for the producer and its consumer; the rounding the TP
-    path's all-reduce input has).  On the CPU ``w`` is row-major."""
+    path's all-reduce input has).  On the CPU ``w`` is row-major.
+
+    ``w_exps`` (FP8 weights, W8A16): ``w`` is the uint8 ``shuffle_weights_fp8`` copy of the e4m3fn
+    bytes and ``w_exps`` [N] the rows' exponent bytes (``weight_quantize_fp8``); the result is, bit
+    for bit, what the bf16 kernel gives on ``shuffle_weights(weight_dequantize_fp8(...))``.  Only
+    the configurations with ``native().stream_gemm_fp8_ok(cfg)``; K % 64 == 0."""
+    fp8 = w_exps is not None
     if not x.is_cuda:
+        if fp8:
+            w = weight_dequantize_fp8(w, w_exps).to(x.dtype)
         y = _ref_stream_gemm(x, w, splits=splits, epilogue=epilogue, residual=residual, norm_eps=norm_eps)
         return y.to(slab_dtype) if splits > 1 else y
     expect(norm_eps <= 0 or residual is None, "the consumer RMSNorm takes no residual add")
-    expect(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "bf16 operands required")
+    if fp8:
+        expect(x.dtype == torch.bfloat16 and w.dtype == torch.uint8, "FP8 weights: bf16 x, uint8 fragment copy")
+        expect(native().stream_gemm_fp8_ok(cfg), f"stream_gemm cfg {cfg} has no FP8-weight instantiation")
+        expect(w.dim() == 2 and w.shape[1] % 64 == 0, "FP8 weights need K % 64 == 0")
+        expect(w_exps.dtype == torch.uint8 and w_exps.is_cuda and w_exps.dim() == 1 and w_exps.shape[0] == w.shape[0]
+               and w_exps.is_contiguous() and w_exps.data_ptr() % 4 == 0,
+               "w_exps must be the uint8 [N] row exponents (contiguous, 4-byte aligned)")
+    else:
+        expect(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "bf16 operands required")
     expect(x.stride(-1) == 1 and w.stride(-1) == 1, "operands must be K-contiguous")
     M, K = x.shape
     N = w.shape[0]
@@ -941,6 +985,12 @@ def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=F
             out = torch.empty((M, n_out), dtype=torch.bfloat16, device=x.device)
         expect(out.dtype == torch.bfloat16 and out.stride(-1) == 1 and tuple(out.shape) == (M, n_out), "bad output")
         ldo = out.stride(0)
+    if fp8:
+        native().stream_gemm_fp8(ptr(x), x.stride(0), ptr(w), ptr(w_exps), ptr(out), ldo, ptr(residual),
+                                 residual.stride(0) if residual is not None else 0, M, N, K, splits, int(epilogue),
+                                 stream(x), int(bool(nt)), int(cfg), float(norm_eps),
+                                 int(splits > 1 and out.dtype == torch.bfloat16), int(w_group))
+        return out
     native().stream_gemm(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(out), ldo, ptr(residual),
                          residual.stride(0) if residual is not None else 0, M, N, K, splits, int(epilogue), stream(x),
                          int(bool(nt)), int(cfg), float(norm_eps), int(splits > 1 and out.dtype == torch.bfloat16),

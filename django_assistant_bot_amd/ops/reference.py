@@ -194,6 +194,18 @@ def kv_dequantize(data, exps):
     return data.view(torch.float8_e4m3fn).float() * scale[..., None]
 
 
+def weight_quantize_fp8(w):
+    """Projection weights [N, K] -> (e4m3fn bytes uint8 [N, K], exponent bytes uint8 [N]): the KV
+    cache's row rule (``kv_quantize``) along K, one power-of-two scale per output row.  Load-time,
+    in torch.  docs/ARCHITECTURE.md "FP8 weights"."""
+    return kv_quantize(w)
+
+
+def weight_dequantize_fp8(data, exps):
+    """(bytes [N, K], exponent bytes [N]) -> bf16 [N, K]; exact (every value is bf16-exact)."""
+    return kv_dequantize(data, exps).to(torch.bfloat16)
+
+
 def rope_kv_write_fp8(qkv, positions, cos_sin, k_data, k_exp, v_data, v_exp, slots, Hq, Hkv, D, block_size):
     """``rope_kv_write`` into an FP8 cache: what the bf16 cache would hold is quantised per row."""
     T = qkv.shape[0]

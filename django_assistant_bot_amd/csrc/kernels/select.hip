@@ -103,12 +103,17 @@ __device__ uint32_t radix_kth(KeyAt key_at, int n, int k, SelShared& sh, uint32_
   return prefix;
 }
 
+struct SelIdentity {
+  __device__ __forceinline__ int operator()(int i) const { return i; }
+};
+
 // Gathers the k largest keys (ties at the k-th key taken in arbitrary order) into sh.cand_*[0..k)
 // and sorts them descending by key (ascending index among equal keys).  TIES_ALL: every key equal
 // to the k-th is kept too (HF TopKLogitsWarper keeps all logits >= the k-th value), up to SEL_MAXK
-// candidates; returns the number kept (k without TIES_ALL).
-template <bool TIES_ALL = false, class KeyAt>
-__device__ int select_topk(KeyAt key_at, int n, int k, SelShared& sh) {
+// candidates; returns the number kept (k without TIES_ALL).  idx_at(i): the index entry i is sorted
+// and reported by (i itself, or the row index a candidate list carries for its entry i).
+template <bool TIES_ALL = false, class KeyAt, class IdxAt = SelIdentity>
+__device__ int select_topk(KeyAt key_at, int n, int k, SelShared& sh, IdxAt idx_at = IdxAt()) {
   const int tid = threadIdx.x;
   uint32_t ties;
   const uint32_t kth = radix_kth(key_at, n, k, sh, ties);
@@ -130,12 +135,12 @@ __device__ int select_topk(KeyAt key_at, int n, int k, SelShared& sh) {
     const int pg = wave_append(&sh.cnt_gt, i < n && key > kth);
     if (pg >= 0) {
       sh.cand_key[pg] = key;
-      sh.cand_idx[pg] = i;
+      sh.cand_idx[pg] = idx_at(i);
     }
     const int pe = wave_append(&sh.cnt_eq, i < n && key == kth);
     if (pe >= 0 && (uint32_t)pe < ties) {
       sh.cand_key[n_gt + pe] = key;
-      sh.cand_idx[n_gt + pe] = i;
+      sh.cand_idx[n_gt + pe] = idx_at(i);
     }
   }
   __syncthreads();
@@ -283,7 +288,7 @@ __global__ __launch_bounds__(CH_NT) void chunk_topk_kernel(const void* __restric
                                                            int k, int kc, uint32_t* __restrict__ cand_key,
                                                            int* __restrict__ cand_idx, int index_base = 0) {
   __shared__ uint32_t hist[256];
-  __shared__ uint32_t bc[2];
+  __shared__ uint32_t bc[3];
   __shared__ uint32_t cnt[2];
   __shared__ ChunkFast fst;
   const int row = blockIdx.y, c = blockIdx.x, nchunks = gridDim.x;
@@ -406,7 +411,7 @@ __global__ __launch_bounds__(CH_NT) void chunk_topk_kernel(const void* __restric
     }
     __syncthreads();  // uniform: every thread read the same count
   }
-  uint32_t prefix = 0, pmask = 0, need = (uint32_t)kk;
+  uint32_t prefix = 0, pmask = 0, need = (uint32_t)kk, ntie = 0;
   for (int shift = 24; shift >= 0; shift -= 8) {
     for (int i = tid; i < 256; i += CH_NT) hist[i] = 0;
     __syncthreads();
@@ -447,6 +452,7 @@ __global__ __launch_bounds__(CH_NT) void chunk_topk_kernel(const void* __restric
           if (acc + cc[j] >= need) {
             bc[0] = 255u - 4u * tid - j;
             bc[1] = need - acc;
+            bc[2] = cc[j];  // after the last pass: the keys equal to the kk-th
             break;
           }
           acc += cc[j];
@@ -457,6 +463,7 @@ __global__ __launch_bounds__(CH_NT) void chunk_topk_kernel(const void* __restric
     prefix |= bc[0] << shift;
     pmask |= 255u << shift;
     need = bc[1];
+    ntie = bc[2];
     __syncthreads();
   }
   if (tid == 0) {
@@ -465,6 +472,34 @@ __global__ __launch_bounds__(CH_NT) void chunk_topk_kernel(const void* __restric
   }
   __syncthreads();
   const uint32_t n_gt = (uint32_t)kk - need;
+  // More keys tie at the kk-th value than slots are left (a greedy row with hundreds of equal maxima):
+  // the lowest indices are taken, not the first to arrive -- the argmax of the merge is the lowest tied
+  // index only if the chunk that holds it hands it on.  Rare, so done plainly: every thread publishes
+  // the tie bits of its PT keys (in the histogram's LDS) and counts the ties ahead of each of its vectors
+  // that holds one; (vector, thread, element) ascending is idx_of ascending.
+  const bool ordered = ntie > need;
+  if (ordered) {
+    static_assert(PT == 32, "one tie bit per key in a 32-bit word");
+    uint32_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < PT; ++j) mine |= (uint32_t)(idx_of(j) < len && key[j] == prefix) << j;
+    hist[tid] = mine;
+    __syncthreads();
+    // (a tied key is `prefix` and its index follows from its bit, so key[] is not indexed here)
+    for (int v = 0; v < (PT >> lg); ++v) {
+      const int b0 = v << lg, b1 = (v + 1) << lg;
+      uint32_t bits = (mine >> b0) & ((1u << (1 << lg)) - 1u);
+      if (!bits) continue;
+      const uint32_t m0 = (1u << b0) - 1u, m1 = b1 >= 32 ? 0xffffffffu : (1u << b1) - 1u;
+      uint32_t pe = __popc(mine & m0);  // ties with a lower index: this thread's earlier vectors, ...
+      for (int t = 0; t < CH_NT; ++t)   // ... the other threads' up to this vector (before it from tid on)
+        if (t != tid) pe += __popc(hist[t] & (t < tid ? m1 : m0));
+      for (; bits && pe < need; bits &= bits - 1u, ++pe) {
+        ok[n_gt + pe] = prefix;
+        oi[n_gt + pe] = index_base + start + idx_of(b0 + __ffs((int)bits) - 1);
+      }
+    }
+  }
 #pragma unroll
   for (int j = 0; j < PT; ++j) {
     const int i = idx_of(j);
@@ -474,6 +509,7 @@ __global__ __launch_bounds__(CH_NT) void chunk_topk_kernel(const void* __restric
       ok[pg] = key[j];
       oi[pg] = index_base + start + i;
     }
+    if (ordered) continue;  // (uniform)
     const int pe = wave_append(&cnt[1], valid && key[j] == prefix);
     if (pe >= 0 && (uint32_t)pe < need) {
       ok[n_gt + pe] = key[j];
@@ -583,10 +619,12 @@ __global__ __launch_bounds__(SEL_NT) void topk_merge_kernel(const uint32_t* __re
   const uint32_t* ck = cand_key + (size_t)row * ncand;
   const int* ci = cand_idx + (size_t)row * ncand;
   auto key_at = [&](int i) -> uint32_t { return ck[i]; };
-  select_topk(key_at, ncand, k, sh);
+  // equal keys are ordered by row index: the chunk stage's radix arm emits its candidates in arrival
+  // order, so their place in the list says nothing about it
+  auto idx_at = [&](int i) -> int { return ci[i]; };
+  select_topk(key_at, ncand, k, sh, idx_at);
   for (int i = threadIdx.x; i < k; i += SEL_NT) {
-    const int pos = sh.cand_idx[i];
-    const int idx = (pos >= 0 && pos < ncand) ? ci[pos] : -1;
+    const int idx = sh.cand_idx[i];
     out_vals[(size_t)row * k + i] = key_float(sh.cand_key[i]);
     if (out_idx) out_idx[(size_t)row * k + i] = idx;
     if (out_idx64) out_idx64[(size_t)row * k + i] = idx >= 0 ? index_base + idx : -1;

@@ -13,6 +13,9 @@ query batch:
 
     python benchmarks/index_bench.py --rows 10000000 --batch 1 64 512
     python benchmarks/index_bench.py --gpus 8 ...     (starts its 8 ranks itself; or one rank under torchrun)
+    python benchmarks/index_bench.py --dtype fp8 ...  (the opt-in FP8 index: dim + 1 bytes per row)
+    python benchmarks/index_bench.py --dtype fp8 --rows 1000000 --recall 256
+                                                      (+ recall@10 / @k against a bf16 index of the same vectors)
 
 Reported per query batch size: latency per search call (max over ranks), queries/s over the whole
 job, and the effective scan rate (index bytes read per second, summed over ranks).
@@ -42,6 +45,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sample-stride", type=int, default=0,
                     help="A/B: the threshold search's row-sample stride (0 = VectorIndex default)")
+    ap.add_argument("--dtype", choices=("bf16", "fp8"), default="bf16", help="index storage: bf16 rows or FP8 rows")
+    ap.add_argument("--recall", type=int, default=0, metavar="Q",
+                    help="with --dtype fp8 on one GPU: recall@10 and @k of Q random queries against a bf16 index "
+                         "built from the same vectors")
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", 1)),
                     help="ranks; from a plain process the script starts them itself (parallel/launch.py)")
     args = ap.parse_args()
@@ -60,13 +67,26 @@ def main():
     info = pdist.init()
     check_world(args.gpus, info.world_size)
     dev, W, R = info.device, info.world_size, info.rank
-    index = ShardedIndex(args.dim, dev, capacity=args.rows // W + 1024)
-    g = torch.Generator(device=dev).manual_seed(7 + R)
     mine = np.arange(R, args.rows, W, dtype=np.int64)
-    for s in range(0, len(mine), 1 << 20):
-        ids = mine[s:s + (1 << 20)]
-        index.add(ids, torch.randn((len(ids), args.dim), device=dev, generator=g), doc_ids=ids // 10,
-                  groups=np.zeros(len(ids), dtype=np.int32))
+
+    def build(dtype):
+        index = ShardedIndex(args.dim, dev, capacity=args.rows // W + 1024, dtype=dtype)
+        g = torch.Generator(device=dev).manual_seed(7 + R)
+        for s in range(0, len(mine), 1 << 20):
+            ids = mine[s:s + (1 << 20)]
+            index.add(ids, torch.randn((len(ids), args.dim), device=dev, generator=g), doc_ids=ids // 10,
+                      groups=np.zeros(len(ids), dtype=np.int32))
+        return index, g
+
+    cuda = dev.type == "cuda"
+    if cuda:
+        torch.cuda.synchronize(dev)
+    mem0 = torch.cuda.memory_allocated(dev) if cuda else 0
+    index, g = build(args.dtype)
+    if cuda:
+        torch.cuda.synchronize(dev)
+    index_bytes = (torch.cuda.memory_allocated(dev) - mem0) if cuda else 0
+    row_bytes = args.dim + 1 if args.dtype == "fp8" else args.dim * 2
     results = []
     for B in args.batch:
         q = torch.randn((B, args.dim), device=dev, generator=g)
@@ -85,13 +105,25 @@ def main():
         per_call = el / args.iters
         res = {"queries_per_rank": B, "ms_per_search": round(1000 * per_call, 3),
                "queries_per_s": round(W * B / per_call, 1),
-               "scan_TBps": round(args.rows * args.dim * 2 / per_call / 1e12, 2)}
+               "scan_TBps": round(args.rows * row_bytes / per_call / 1e12, 2)}
         results.append(res)
         assert ids.shape == (B, args.k)
+    extra = {}
+    if args.recall and args.dtype == "fp8" and W == 1:
+        # the FP8 index's exact top-k over its quantised rows against the bf16 index's over the same vectors
+        q = torch.randn((args.recall, args.dim), device=dev, generator=torch.Generator(device=dev).manual_seed(99))
+        exact, _ = build("bf16")
+        for kk in sorted({10, args.k}):
+            hit = 0
+            for a in range(0, args.recall, 64):
+                got = index.search(q[a:a + 64], kk)[1].cpu().numpy()
+                want = exact.search(q[a:a + 64], kk)[1].cpu().numpy()
+                hit += sum(len(np.intersect1d(x, y)) for x, y in zip(got, want))
+            extra[f"recall_at_{kk}_vs_bf16"] = round(hit / (args.recall * kk), 4)
     if R == 0:
         print(json.dumps({"metric": "sharded in-HBM cosine top-k (RCCL all_to_all merge)", "n_gpus": W,
-                          "rows": args.rows, "dim": args.dim, "k": args.k, "dtype": "bf16", "data": "synthetic",
-                          "results": results}), flush=True)
+                          "rows": args.rows, "dim": args.dim, "k": args.k, "dtype": args.dtype, "data": "synthetic",
+                          "index_bytes_allocated": index_bytes, **extra, "results": results}), flush=True)
     pdist.shutdown()
 
 

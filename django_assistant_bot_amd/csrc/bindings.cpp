@@ -260,6 +260,20 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("A"), py::arg("lda"), py::arg("Wshuf"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("row_group"),
      py::arg("q_group"), py::arg("thr"), py::arg("cnt"), py::arg("cand_val"), py::arg("cand_idx"), py::arg("cap"),
      py::arg("s"), py::arg("b_rows") = 0);
+  m.def("score_candidates_fp8", [](u A, long lda, u W8, u exps, int M, int N, int K, u row_group, u q_group, u thr,
+                                   u cnt, u cand_val, u cand_idx, int cap, u s) {
+    check(dab::index_scan_candidates_fp8(CVP(A), lda, CVP(W8), CVP(exps), M, N, K,
+                                         reinterpret_cast<const int*>(row_group), reinterpret_cast<const int*>(q_group),
+                                         reinterpret_cast<const float*>(thr), reinterpret_cast<int*>(cnt),
+                                         reinterpret_cast<float*>(cand_val), reinterpret_cast<int*>(cand_idx), cap, ST(s)),
+          "score_candidates_fp8");
+  }, py::arg("A"), py::arg("lda"), py::arg("W8"), py::arg("exps"), py::arg("M"), py::arg("N"), py::arg("K"),
+     py::arg("row_group"), py::arg("q_group"), py::arg("thr"), py::arg("cnt"), py::arg("cand_val"), py::arg("cand_idx"),
+     py::arg("cap"), py::arg("s"));
+  m.def("index_dequant_blocks", [](u data, u exps, u out, long b0, long b1, long out_block, int K, u s) {
+    check(dab::index_dequant_blocks(CVP(data), CVP(exps), VP(out), b0, b1, out_block, K, ST(s)), "index_dequant_blocks");
+  }, py::arg("data"), py::arg("exps"), py::arg("out"), py::arg("b0"), py::arg("b1"), py::arg("out_block"), py::arg("K"),
+     py::arg("s"));
   m.def("stream_gemm", [](u X, long ldx, u W, long ldw, u out, long ldo, u residual, long ldr, int M, int N, int K,
                           int S, int epilogue, u s, int nt, int cfg, float norm_eps, int slab_bf16, int w_group) {
     check(dab::stream_gemm(CVP(X), ldx, CVP(W), ldw, VP(out), ldo, CVP(residual), ldr, M, N, K, S, epilogue, ST(s), nt,

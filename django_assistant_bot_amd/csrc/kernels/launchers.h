@@ -135,6 +135,16 @@ int index_scan_candidates(const void* X, long ldx, const void* W, long ldw, int 
 int index_scan_candidates_shuf(const void* X, long ldx, const void* W, int M, int N, int K, const int* row_group,
                                const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx,
                                int cap, hipStream_t s);
+// ... and over FP8 rows: e4m3fn bytes in the shuffle_weights_fp8 layout (>= round_up(N, 32) rows) with one
+// exponent byte per row (4-byte aligned, >= round_up(N, 4) bytes); score = fp32 sum x 2^(byte - 127), bit-equal
+// to the bf16 scan over the dequantised rows.  Same M / K limits.
+int index_scan_candidates_fp8(const void* X, long ldx, const void* W, const void* exps, int M, int N, int K,
+                              const int* row_group, const int* q_group, const float* thr, int* cnt, float* cand_val,
+                              int* cand_idx, int cap, hipStream_t s);
+// 16-row blocks [b0, b1) of that FP8 copy -> bf16 in the shuffle_weights layout, blocks out_block .. of `out`
+// (exact: every dequantised value is a bf16).  K % 64 == 0.
+int index_dequant_blocks(const void* data, const void* exps, void* out, long b0, long b1, long out_block, int K,
+                         hipStream_t s);
 int stream_score_candidates(const void* X, long ldx, const void* W, long ldw, int M, int N, int K, const int* row_group,
                             const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx, int cap,
                             hipStream_t s);

@@ -18,8 +18,22 @@ layout: every 16-row x 32-k block is one coalesced 1 KB load for the 1..128-quer
 GEMM at >= 128 queries and the generic-filter score GEMM.  (Round 2 kept a row-major copy beside
 it: 2x the index HBM.)  Only the 1/64 row sample of the threshold search is gathered row-major, and
 cached until the next update.
+
+FP8 rows (opt-in: ``dtype=torch.float8_e4m3fn`` / ``"fp8"``, or ``DAB_INDEX_DTYPE=fp8`` when no dtype
+is given; docs/ARCHITECTURE.md "FP8 vector index").  A row is normalised and rounded to bf16 as above,
+then quantised with ``ops.kv_quantize``: ``dim`` e4m3fn bytes and one power-of-two exponent byte,
+``dim + 1`` bytes per row instead of ``2 dim``.  On the GPU (dim % 256 == 0, dim <= 1024) the bytes
+are held once, in the ``ops.shuffle_weights_fp8`` fragment layout, with the exponents in a uint8
+tensor beside them; the threshold search streams them with the FP8 arm of index_scan.hip (batches
+above 96 queries -- 64 at dim 1024 -- in groups), and every search that needs a score matrix
+(``allowed`` / ``doc_lt`` filters, small indexes, the overflow fallback) dequantises row chunks into
+a bf16 scratch (``ops.index_dequant_blocks``, exact) for the unchanged bf16 GEMM.  On the CPU the
+bytes are row-major and scores are computed over the dequantised rows.  The search is exact over
+the QUANTISED rows: recall against the unquantised vectors is no longer 1.0 by construction.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -28,11 +42,42 @@ import torch.nn.functional as F
 from .. import ops
 
 
+FP8 = torch.float8_e4m3fn
+
+
+def parse_index_dtype(name) -> torch.dtype:
+    """Index storage dtype from a setting: a ``torch.dtype``, the name of one (``"bfloat16"``,
+    ``"float8_e4m3fn"``, ...) or the aliases ``"fp8"`` / ``"bf16"``."""
+    if isinstance(name, torch.dtype):
+        return name
+    key = str(name).strip().lower()
+    alias = {"fp8": FP8, "bf16": torch.bfloat16}
+    dt = alias.get(key, getattr(torch, key, None))
+    if not isinstance(dt, torch.dtype):
+        raise ValueError(f"unknown index dtype {name!r}")
+    return dt
+
+
+def default_index_dtype() -> torch.dtype:
+    """``DAB_INDEX_DTYPE`` if set, else bf16: what ``VectorIndex(dtype=None)`` stores."""
+    env = os.environ.get("DAB_INDEX_DTYPE")
+    return parse_index_dtype(env) if env else torch.bfloat16
+
+
 class VectorIndex:
-    def __init__(self, dim: int, device=None, capacity: int = 4096, dtype=torch.bfloat16):
+    def __init__(self, dim: int, device=None, capacity: int = 4096, dtype=None):
         self.dim = dim
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
-        self.dtype = dtype
+        dtype = self.dtype = default_index_dtype() if dtype is None else parse_index_dtype(dtype)
+        # FP8 rows: e4m3fn bytes in ``vecs`` (uint8) + one exponent byte per row in ``exps``; on the GPU
+        # in the FP8 fragment layout (``frag8``), which the scan kernel serves at these widths only
+        self.fp8 = dtype == FP8
+        self.frag8 = self.fp8 and self.device.type == "cuda"
+        if self.frag8 and (dim % 256 or dim > 1024):
+            raise ValueError(f"an FP8 index on the GPU needs dim % 256 == 0 and dim <= 1024, got {dim}")
+        self.qdtype = torch.bfloat16 if self.fp8 else dtype  # what normalised rows / queries are rounded to
+        self.exps = None
+        self._scratch = None  # bf16 fragment scratch of the FP8 score-matrix path
         self._cap = 0
         self.n = 0  # rows in use (live + tombstoned)
         self.stats = {"threshold_searches": 0, "threshold_overflows": 0}
@@ -50,12 +95,13 @@ class VectorIndex:
     def _grow(self, cap: int):
         cap = (cap + 255) // 256 * 256  # whole 256-row tiles for the fragment-layout scans / GEMMs
         dev = self.device
-        vecs = torch.zeros((cap, self.dim), dtype=self.dtype, device=dev)
+        vecs = torch.zeros((cap, self.dim), dtype=torch.uint8 if self.fp8 else self.dtype, device=dev)
+        exps = torch.full((cap,), 127, dtype=torch.uint8, device=dev) if self.fp8 else None
         ids = torch.full((cap,), -1, dtype=torch.int64, device=dev)
         docs = torch.full((cap,), -1, dtype=torch.int64, device=dev)
         grp = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         if self.n:
-            if self.frag:  # the first ceil(n / 16) 16-row blocks are a contiguous prefix
+            if self.frag or self.frag8:  # the first ceil(n / 16) 16-row blocks are a contiguous prefix
                 e = -(-self.n // 16) * 16 * self.dim
                 vecs.view(-1)[:e] = self.vecs.view(-1)[:e]
             else:
@@ -63,6 +109,9 @@ class VectorIndex:
             ids[: self.n] = self.row_ids[: self.n]
             docs[: self.n] = self.row_docs[: self.n]
             grp[: self.n] = self.row_group[: self.n]
+            if self.fp8:
+                exps[: self.n] = self.exps[: self.n]
+        self.exps = exps
         self.vecs, self.row_ids, self.row_docs, self.row_group = vecs, ids, docs, grp
         self._cap = cap
 
@@ -73,15 +122,36 @@ class VectorIndex:
     # 10M rows x 512 queries 10.79 -> 9.15 ms, 128 queries 4.70 -> 4.59; profiles/index_search.md)
     sample_stride = 64
 
+    def _put_fp8(self, rows: torch.Tensor, data: torch.Tensor, exps: torch.Tensor) -> None:
+        """Stores quantised rows (bytes [n, dim], exponent bytes [n]) as they are."""
+        if self.frag8:
+            ops.shuffle_rows_into_fp8(self.vecs, rows, data)
+        else:
+            self.vecs[rows] = data
+        self.exps[rows] = exps
+
+    def _rows_fp8(self, rows: torch.Tensor):
+        """(bytes [n, dim] row-major, exponent bytes [n]) of the given rows of an FP8 index."""
+        if not self.frag8:
+            return self.vecs[rows], self.exps[rows]
+        R, K = self.vecs.shape
+        v6 = self.vecs.view(R // 16, K // 64, 4, 16, 2, 8)
+        data = v6[rows // 16, :, :, rows % 16].permute(0, 1, 3, 2, 4).reshape(rows.numel(), K)
+        return data, self.exps[rows]
+
     def _put(self, rows: torch.Tensor, v: torch.Tensor) -> None:
-        if self.frag:
+        if self.fp8:
+            self._put_fp8(rows, *ops.kv_quantize(v.to(torch.bfloat16)))
+        elif self.frag:
             ops.shuffle_rows_into(self.vecs, rows, v)
         else:
             self.vecs[rows] = v
 
     def rows_data(self, rows) -> torch.Tensor:
-        """Row-major copy of the given rows (any layout)."""
+        """Row-major copy of the given rows (any layout); FP8 rows dequantised to bf16 (exact)."""
         rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
+        if self.fp8:
+            return ops.weight_dequantize_fp8(*self._rows_fp8(rows))
         if not self.frag:
             return self.vecs[rows]
         R, K = self.vecs.shape
@@ -94,15 +164,22 @@ class VectorIndex:
     def __contains__(self, item_id: int) -> bool:
         return int(item_id) in self._row_of
 
-    def add(self, ids, vectors, doc_ids=None, groups=None) -> None:
+    def add(self, ids, vectors, doc_ids=None, groups=None, quantised=None) -> None:
         """Upsert rows.  ids: int64 [n]; vectors [n, dim] (any float dtype / device); doc_ids int64 [n]
-        (document each row belongs to); groups int32 [n] (e.g. bot id; must be >= 0)."""
+        (document each row belongs to); groups int32 [n] (e.g. bot id; must be >= 0).  ``quantised``
+        (FP8 indexes; ``vectors`` is ignored): (bytes uint8 [n, dim], exponent bytes uint8 [n]) of rows
+        another FP8 index held, stored as they are (snapshots)."""
         ids = np.asarray(ids, dtype=np.int64).reshape(-1)
         n = len(ids)
         if n == 0:
             return
-        v = torch.as_tensor(vectors).to(self.device, torch.float32).reshape(n, self.dim)
-        v = F.normalize(v, dim=-1).to(self.dtype)
+        if quantised is not None:
+            if not self.fp8:
+                raise ValueError("quantised rows need an FP8 index")
+            v = None
+        else:
+            v = torch.as_tensor(vectors).to(self.device, torch.float32).reshape(n, self.dim)
+            v = F.normalize(v, dim=-1).to(self.qdtype)
         docs = np.full(n, -1, dtype=np.int64) if doc_ids is None else np.asarray(doc_ids, dtype=np.int64)
         grp = np.zeros(n, dtype=np.int32) if groups is None else np.asarray(groups, dtype=np.int32)
         if (grp < 0).any():
@@ -139,7 +216,10 @@ class VectorIndex:
             x = torch.from_numpy(np.ascontiguousarray(a))
             return (x.pin_memory() if pin else x).to(self.device, non_blocking=True)
         r = dev(rows)
-        self._put(r, v)
+        if quantised is not None:
+            self._put_fp8(r, quantised[0].to(self.device).reshape(n, self.dim), quantised[1].to(self.device).reshape(n))
+        else:
+            self._put(r, v)
         self._version += 1
         self.row_ids[r] = dev(ids)
         self.row_docs[r] = dev(docs)
@@ -161,7 +241,10 @@ class VectorIndex:
     def compact(self) -> None:
         live = (self.row_group[: self.n] >= 0).nonzero().flatten()
         m = live.numel()
-        self._put(torch.arange(m, device=self.device), self.rows_data(live))
+        if self.fp8:  # the bytes and exponents move as they are: nothing is quantised twice
+            self._put_fp8(torch.arange(m, device=self.device), *self._rows_fp8(live))
+        else:
+            self._put(torch.arange(m, device=self.device), self.rows_data(live))
         self._version += 1
         self.row_ids[:m] = self.row_ids[live]
         self.row_docs[:m] = self.row_docs[live]
@@ -225,7 +308,7 @@ class VectorIndex:
         """fp32 cosine similarities [q, n] (-inf for filtered / deleted rows).  Filters: ``q_groups``
         (per-query row group, e.g. bot + status bit), ``allowed`` (per-query item ids), ``doc_lt``
         (per-query document-id bound); masks are ANDed."""
-        q = F.normalize(torch.as_tensor(queries).to(self.device, torch.float32), dim=-1).to(self.dtype)
+        q = F.normalize(torch.as_tensor(queries).to(self.device, torch.float32), dim=-1).to(self.qdtype)
         qg = None if q_groups is None else torch.as_tensor(q_groups, dtype=torch.int32).to(self.device)
         allow = None if allowed is None else self.allow_mask(allowed)
         if doc_lt is not None:
@@ -233,11 +316,35 @@ class VectorIndex:
             allow = dm if allow is None else allow & dm
         n = max(self.n, 4)
         n = (n + 3) // 4 * 4
+        if self.frag8:
+            return self._scores_fp8(q, n, qg, allow)
+        if self.fp8:  # CPU: the bf16 path's reference over the dequantised rows
+            return ops.gemm_bt(q, ops.weight_dequantize_fp8(self.vecs[:n], self.exps[:n]), epilogue=ops.EPI_SCORES,
+                               out_f32=True, row_group=self.row_group[:n], q_group=qg, allow=allow)
         if self.frag:
             return ops.gemm_bt(q, self.vecs, epilogue=ops.EPI_SCORES, out_f32=True, row_group=self.row_group[:n],
                                q_group=qg, allow=allow, shuffled=True, n=n)
         return ops.gemm_bt(q, self.vecs[:n], epilogue=ops.EPI_SCORES, out_f32=True, row_group=self.row_group[:n],
                            q_group=qg, allow=allow)
+
+    SCORE_SCRATCH_BYTES = 256 << 20  # bf16 scratch of the FP8 index's score-matrix path
+
+    def _scores_fp8(self, q, n: int, qg, allow) -> torch.Tensor:
+        """``scores`` of a GPU FP8 index: row chunks (whole 256-row groups, so the allow bitmask
+        splits on word boundaries) are dequantised into a reusable bf16 fragment scratch and scored by
+        the bf16 GEMM with the chunk's ``row_group`` slice and mask words, side by side in one matrix."""
+        chunk = max(256, self.SCORE_SCRATCH_BYTES // (2 * self.dim) // 256 * 256)
+        rows = min(chunk, -(-n // 256) * 256)
+        if self._scratch is None or self._scratch.shape[0] != rows:
+            self._scratch = torch.zeros((rows, self.dim), dtype=torch.bfloat16, device=self.device)
+        out = torch.empty((q.shape[0], n), dtype=torch.float32, device=self.device)
+        for r0 in range(0, n, chunk):
+            r1 = min(n, r0 + chunk)
+            ops.index_dequant_blocks(self.vecs, self.exps, r0 // 16, -(-r1 // 256) * 16, self._scratch, 0)
+            aw = None if allow is None else allow[:, r0 // 32: -(-r1 // 32)].contiguous()
+            ops.gemm_bt(q, self._scratch, epilogue=ops.EPI_SCORES, out_f32=True, row_group=self.row_group[r0:r1],
+                        q_group=qg, allow=aw, shuffled=True, n=r1 - r0, out=out[:, r0:r1])
+        return out
 
     @torch.inference_mode()
     def search(self, queries, k: int, q_groups=None, allowed=None, doc_lt=None):
@@ -274,7 +381,7 @@ class VectorIndex:
         appends only scores >= that bound (about 16k per query on unstructured data), and an exact
         top-k runs over those.  A chunk whose candidate list overflows is retried or scanned on its
         own (``_threshold_chunk``)."""
-        q = F.normalize(torch.as_tensor(queries).to(self.device, torch.float32), dim=-1).to(self.dtype)
+        q = F.normalize(torch.as_tensor(queries).to(self.device, torch.float32), dim=-1).to(self.qdtype)
         qg = None if q_groups is None else torch.as_tensor(q_groups, dtype=torch.int32).to(self.device)
         n4 = (self.n + 3) // 4 * 4
         ns = (self.n // self.sample_stride) // 4 * 4
@@ -327,7 +434,15 @@ class VectorIndex:
     CAND_BYTES = 256 << 20  # candidate-list memory of one threshold search
 
     def _threshold_candidates(self, q, thr, k: int, cap: int, n4: int, qg):
-        if self.frag:
+        if self.frag8:  # the FP8 scan, in groups of the queries one launch takes
+            step = ops.fp8_scan_max_m(self.dim)
+            parts = [ops.score_candidates_fp8(q[a:a + step], self.vecs, self.exps, n4, thr[a:a + step], cap,
+                                              self.row_group[:n4], None if qg is None else qg[a:a + step])
+                     for a in range(0, q.shape[0], step)]
+            cand_val, cand_idx, cnt = parts[0]
+            if len(parts) > 1:
+                cand_val, cand_idx, cnt = (torch.cat([p[i] for p in parts]) for i in range(3))
+        elif self.frag:
             cand_val, cand_idx, cnt = ops.score_candidates_shuffled(q, self.vecs, n4, thr, cap, self.row_group[:n4], qg)
         else:
             cand_val, cand_idx, cnt = ops.score_candidates(q, self.vecs[:n4], thr, cap, self.row_group[:n4], qg)
@@ -357,6 +472,13 @@ class VectorIndex:
         from safetensors.torch import save_file
 
         n = self.n
+        if self.fp8:
+            data, exps = self._rows_fp8(torch.arange(n, device=self.device))
+            save_file({"vecs_fp8": data.contiguous().cpu(), "exps": exps.contiguous().cpu(),
+                       "ids": self.row_ids[:n].cpu(), "docs": self.row_docs[:n].cpu(),
+                       "group": self.row_group[:n].cpu()}, path,
+                      metadata={"dim": str(self.dim), "dtype": "float8_e4m3fn"})
+            return
         save_file({"vecs": self.rows_data(torch.arange(n, device=self.device)).contiguous().cpu(),
                    "ids": self.row_ids[:n].cpu(),
                    "docs": self.row_docs[:n].cpu(), "group": self.row_group[:n].cpu()}, path,
@@ -367,9 +489,14 @@ class VectorIndex:
         from safetensors.torch import load_file
 
         st = load_file(path)
-        idx = cls(st["vecs"].shape[1], device, capacity=max(64, st["vecs"].shape[0]), dtype=st["vecs"].dtype)
-        n = st["vecs"].shape[0]
-        idx._put(torch.arange(n, device=idx.device), st["vecs"].to(idx.device))
+        if "vecs_fp8" in st:  # an FP8 snapshot: the bytes and exponents are restored as they are
+            n, dim = st["vecs_fp8"].shape
+            idx = cls(dim, device, capacity=max(64, n), dtype=FP8)
+            idx._put_fp8(torch.arange(n, device=idx.device), st["vecs_fp8"].to(idx.device), st["exps"].to(idx.device))
+        else:
+            idx = cls(st["vecs"].shape[1], device, capacity=max(64, st["vecs"].shape[0]), dtype=st["vecs"].dtype)
+            n = st["vecs"].shape[0]
+            idx._put(torch.arange(n, device=idx.device), st["vecs"].to(idx.device))
         idx.row_ids[:n] = st["ids"].to(idx.device)
         idx.row_docs[:n] = st["docs"].to(idx.device)
         idx.row_group[:n] = st["group"].to(idx.device)

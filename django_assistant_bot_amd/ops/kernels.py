@@ -924,6 +924,85 @@ def unshuffle_weights_fp8(data: torch.Tensor, group: int = 1) -> torch.Tensor:
     return data.reshape(N // 16, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).contiguous().view(N, K)
 
 
+def shuffle_rows_into_fp8(dst: torch.Tensor, rows: torch.Tensor, data: torch.Tensor) -> None:
+    """Writes e4m3fn bytes ``data`` [n, K] (uint8) as rows ``rows`` of ``dst``, a uint8 [R, K] tensor in
+    the ``shuffle_weights_fp8`` layout (group 1): the incremental form of ``shuffle_weights_fp8``, the
+    FP8 counterpart of ``shuffle_rows_into``."""
+    R, K = dst.shape
+    expect(dst.dtype == torch.uint8 and data.dtype == torch.uint8, "shuffle_rows_into_fp8 takes e4m3fn bytes (uint8)")
+    expect(R % 16 == 0 and K % 64 == 0 and dst.is_contiguous(), "FP8 fragment copy: contiguous [R, K], R % 16, K % 64")
+    v6 = dst.view(R // 16, K // 64, 4, 16, 2, 8)  # [blk, j, l >> 4, l & 15, half, 8]
+    rows = rows.to(dst.device, torch.long)
+    v6[rows // 16, :, :, rows % 16, :, :] = data.to(dst.device).reshape(-1, K // 64, 2, 4, 8).permute(0, 1, 3, 2, 4)
+
+
+def fp8_scan_max_m(K: int) -> int:
+    """Most queries one ``score_candidates_fp8`` launch takes at width K (the scan's LDS budget)."""
+    return 96 if K <= 768 else 64
+
+
+def score_candidates_fp8(A, data_shuf, exps, N, thr, cap, row_group=None, q_group=None):
+    """``score_candidates_shuffled`` over FP8 rows: ``data_shuf`` uint8 [R, K], e4m3fn bytes in the
+    ``shuffle_weights_fp8`` layout (R >= round_up(N, 128), R % 16 == 0), ``exps`` uint8 [>= R] with one
+    E8M0 exponent byte per row (``kv_quantize``).  A score is the fp32 sum over the bytes' values times
+    2^(exponent byte - 127): bit-identical to ``score_candidates_shuffled`` on the dequantised rows.
+    The persistent scan of index_scan.hip only: 1..96 queries at K <= 768, 1..64 at K <= 1024,
+    K % 256 == 0 (callers split larger batches)."""
+    expect(A.is_cuda and A.dtype == torch.bfloat16, "bf16 CUDA queries required")
+    M, K = A.shape
+    expect(K % 256 == 0 and K <= 1024 and 1 <= M <= fp8_scan_max_m(K),
+           "FP8 scan: K % 256 == 0, 1..96 queries at K <= 768, 1..64 at K <= 1024")
+    expect(A.stride(-1) == 1 and A.stride(0) % 8 == 0, "queries must be K-contiguous with a row stride % 8 == 0")
+    expect(data_shuf.is_cuda and data_shuf.dtype == torch.uint8 and data_shuf.dim() == 2 and data_shuf.is_contiguous()
+           and data_shuf.shape[1] == K, "FP8 fragment copy: contiguous uint8 [R, K]")
+    expect(data_shuf.shape[0] % 16 == 0 and data_shuf.shape[0] >= -(-N // 128) * 128,
+           "FP8 fragment copy needs round_up(N, 128) rows")
+    expect(exps.is_cuda and exps.dtype == torch.uint8 and exps.dim() == 1 and exps.is_contiguous()
+           and exps.numel() >= -(-N // 128) * 128 and exps.data_ptr() % 4 == 0,
+           "exps: contiguous uint8 [>= round_up(N, 128)], 4-byte aligned")
+    same_device(A, data_shuf, exps, thr)
+    expect(thr.dtype == torch.float32 and thr.is_contiguous() and thr.numel() >= M, "thr must be fp32 [M]")
+    if row_group is not None:
+        _i32(row_group)
+        expect(row_group.numel() >= N, "row_group shorter than N")
+    if q_group is not None:
+        _i32(q_group)
+        expect(q_group.numel() >= M, "q_group shorter than M")
+    cand_val = torch.full((M, cap), float("-inf"), dtype=torch.float32, device=A.device)
+    cand_idx = torch.empty((M, cap), dtype=torch.int32, device=A.device)
+    cnt = torch.zeros(M, dtype=torch.int32, device=A.device)
+    native().score_candidates_fp8(ptr(A), A.stride(0), ptr(data_shuf), ptr(exps), M, int(N), K, ptr(row_group),
+                                  ptr(q_group), ptr(thr), ptr(cnt), ptr(cand_val), ptr(cand_idx), int(cap), stream(A))
+    return cand_val, cand_idx, cnt
+
+
+def index_dequant_blocks(data_shuf, exps, b0: int, b1: int, out, out_block: int = 0):
+    """16-row blocks [b0, b1) of an FP8 fragment copy (``data_shuf`` uint8 [R, K] in the
+    ``shuffle_weights_fp8`` layout, ``exps`` uint8 [>= R]) -> the same rows as bf16 in the
+    ``shuffle_weights`` layout, written to blocks [out_block, out_block + b1 - b0) of ``out`` (bf16
+    [R2, K]); the rest of ``out`` is not touched.  Exact: every dequantised value is a bf16."""
+    R, K = data_shuf.shape
+    b0, b1, out_block = int(b0), int(b1), int(out_block)
+    expect(data_shuf.dtype == torch.uint8 and data_shuf.is_contiguous() and R % 16 == 0 and K % 64 == 0,
+           "FP8 fragment copy: contiguous uint8 [R, K], R % 16 == 0, K % 64 == 0")
+    expect(exps.dtype == torch.uint8 and exps.dim() == 1 and exps.is_contiguous() and exps.numel() >= 16 * b1,
+           "exps: contiguous uint8 with a byte for every row of the blocks")
+    expect(0 <= b0 <= b1 <= R // 16, "blocks [b0, b1) must lie in the copy")
+    expect(out.dtype == torch.bfloat16 and out.dim() == 2 and out.is_contiguous() and out.shape[1] == K
+           and out.shape[0] % 16 == 0 and out_block >= 0 and out_block + (b1 - b0) <= out.shape[0] // 16,
+           "out: contiguous bf16 [R2, K] that holds the blocks")
+    same_device(data_shuf, exps, out)
+    if b1 == b0:
+        return out
+    if not data_shuf.is_cuda:
+        rows = unshuffle_weights_fp8(data_shuf[16 * b0:16 * b1])
+        out[16 * out_block:16 * (out_block + b1 - b0)] = shuffle_weights(
+            weight_dequantize_fp8(rows, exps[16 * b0:16 * b1]))
+        return out
+    native().index_dequant_blocks(ptr(data_shuf), ptr(exps), ptr(out), b0, b1, out_block, K, stream(data_shuf))
+    return out
+
+
 def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=False, cfg=0, norm_eps: float = 0.0,
                 slab_dtype=torch.float32, w_group: int = 1, w_exps=None):
     """Decode GEMM y = x w^T on the warp-specialised streaming kernel (``stream_gemm.hip``): bf16

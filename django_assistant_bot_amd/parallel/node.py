@@ -306,9 +306,10 @@ class Node:
         idx = self.indexes.get(name)
         if idx is None and dim is not None and self.in_index:
             from ..engine.serving import setting
+            from ..engine.vector_index import parse_index_dtype
             from .sharded_index import ShardedIndex
 
-            dtype = getattr(torch, str(setting("INDEX_DTYPE", "bfloat16")))
+            dtype = parse_index_dtype(setting("INDEX_DTYPE", "bfloat16"))
             idx = self.indexes[name] = ShardedIndex(dim, self.device, group=self.index_group, dtype=dtype)
         return idx
 

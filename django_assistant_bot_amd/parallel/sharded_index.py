@@ -27,7 +27,7 @@ from ..engine.vector_index import VectorIndex
 class ShardedIndex:
     SMALL_Q = 16  # queries per rank that travel in the search's first (fixed-size) all_gather
 
-    def __init__(self, dim: int, device=None, group=None, capacity: int = 4096, dtype=torch.bfloat16):
+    def __init__(self, dim: int, device=None, group=None, capacity: int = 4096, dtype=None):
         self.group = group
         # the collective paths run on a group of > 1 ranks, or on any group under DAB_FORCE_GROUP;
         # a 1-rank (sub)group in a larger job searches locally (no gloo staging of a
@@ -92,8 +92,9 @@ class ShardedIndex:
         if not files:
             raise FileNotFoundError(f"no index shards in {directory}")
         with safe_open(files[0], framework="pt") as f:
-            dim = f.get_slice("vecs").get_shape()[1]
-        idx = cls(dim, device, group)
+            fp8 = "vecs_fp8" in f.keys()  # an FP8 index's snapshot: bytes + exponents, restored as they are
+            dim = f.get_slice("vecs_fp8" if fp8 else "vecs").get_shape()[1]
+        idx = cls(dim, device, group, dtype=torch.float8_e4m3fn if fp8 else torch.bfloat16)
         for path in files:
             with safe_open(path, framework="pt") as f:
                 ids = f.get_tensor("ids")
@@ -107,6 +108,10 @@ class ShardedIndex:
                 sel = torch.nonzero(live).view(-1)[torch.from_numpy(np.nonzero(mine)[0])]
                 docs_np = f.get_tensor("docs")[sel].numpy()
                 idx._note_keys(ids_np[mine], docs_np)
+                if fp8:
+                    idx.local.add(ids_np[mine], None, docs_np, f.get_tensor("group")[sel].numpy(),
+                                  quantised=(f.get_tensor("vecs_fp8")[sel], f.get_tensor("exps")[sel]))
+                    continue
                 idx.local.add(ids_np[mine], f.get_tensor("vecs")[sel], docs_np, f.get_tensor("group")[sel].numpy())
         return idx
 

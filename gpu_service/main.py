@@ -178,12 +178,10 @@ class LocalIndexes:
         with self._lock:
             idx = self.indexes.get(name)
             if idx is None:
-                import torch
-
                 from django_assistant_bot_amd.engine.serving import engine_device, setting
-                from django_assistant_bot_amd.engine.vector_index import VectorIndex
+                from django_assistant_bot_amd.engine.vector_index import VectorIndex, parse_index_dtype
 
-                dtype = getattr(torch, str(setting("INDEX_DTYPE", "bfloat16")))
+                dtype = parse_index_dtype(setting("INDEX_DTYPE", "bfloat16"))
                 idx = self.indexes[name] = VectorIndex(len(vectors[0]), device=engine_device(), dtype=dtype)
             idx.add(ids, vectors, doc_ids=doc_ids, groups=groups)
             return len(idx)

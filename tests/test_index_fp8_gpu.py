@@ -1,0 +1,250 @@
+"""The opt-in FP8 vector index on the GPU: ``index_scan_fp8_kernel`` (the FP8 arm of the persistent index scan),
+``index_dequant_kernel`` and ``VectorIndex`` with ``dtype=torch.float8_e4m3fn``.
+
+    test_fp8_scan_exact         every instantiation <MT 1-6, NW 4 / 8> on the exact operands of tests/index_fp8_cases.py
+                                (integer scores, three exponent bytes): M over cand_cases.SCAN_MK at K 256 (ring of 4
+                                chunks), (96, 768) (ring of 6) and (64, 1024) (ring of 8); N 4, 132 and one grid pass +
+                                132; grouped and ungrouped; a dense query with lists that hold everything, and again
+                                with cap = 64.  Verdict: cand_cases.check, no tolerance -- counts, sets, values bit for
+                                bit, guards.  Rows at n >= N (fragment padding, a spare 128-row block) are hot under a
+                                huge exponent byte.
+    test_fp8_scan_bit_equal     random unit rows, quantised: the FP8 scan and the bf16 scan over the dequantised rows
+                                give the same counts, sets and bit-identical values (K 768, one grid pass + 132 rows)
+    test_fp8_scan_wrapper       ops.score_candidates_fp8 refuses what the kernel cannot take
+    test_dequant_blocks         bit-equal to shuffle_weights(weight_dequantize_fp8(...)) on block ranges; sentinels stay
+    test_fp8_index_*            VectorIndex end to end against a bf16 twin that holds its dequantised rows verbatim
+
+tests/test_index_fp8_cpu.py proves the operands and shows that the checker rejects each planted defect."""
+import numpy as np
+import pytest
+import torch
+
+import cand_cases as cc
+import index_fp8_cases as fc
+from django_assistant_bot_amd import ops
+from django_assistant_bot_amd.engine.vector_index import VectorIndex
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+FP8 = torch.float8_e4m3fn
+
+
+def _cus() -> int:
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+# ---------------------------------------------------------------------------------------------
+# the scan
+
+
+@pytest.mark.parametrize("grouped", (True, False))
+@pytest.mark.parametrize("M,K", cc.SCAN_MK)
+def test_fp8_scan_exact(M, K, grouped):
+    for N in cc.scan_ns(_cus()):
+        got = fc.run(ops, DEV, M, N, K, grouped)
+        assert got == [], (M, N, K, grouped, got)
+
+
+@pytest.fixture(scope="module")
+def unit_rows():
+    """Random unit rows of 768, quantised, as (FP8 fragment copy, exponents, bf16 fragment copy of the dequantised
+    rows, N, dequantised row-major rows)."""
+    N, K = cc.scan_pass_rows(_cus()) + 132, 768
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    v = torch.nn.functional.normalize(torch.randn((N, K), generator=g), dim=-1).to(torch.bfloat16).to(DEV)
+    data, exps = ops.kv_quantize(v)
+    assert len(set(exps.cpu().tolist())) >= 2
+    R = -(-N // 128) * 128
+    full = torch.zeros((R, K), dtype=torch.uint8, device=DEV)
+    full[:N] = data
+    efull = torch.full((R,), 127, dtype=torch.uint8, device=DEV)
+    efull[:N] = exps
+    deq = ops.weight_dequantize_fp8(full, efull)
+    return ops.shuffle_weights_fp8(full), efull, ops.shuffle_weights(deq), N, deq
+
+
+@pytest.mark.parametrize("M", (1, 33, 96))
+def test_fp8_scan_bit_equal(unit_rows, M):
+    shuf8, exps, shuf16, N, deq = unit_rows
+    K = shuf8.shape[1]
+    g = torch.Generator(device="cpu").manual_seed(99 + M)
+    q = torch.nn.functional.normalize(torch.randn((M, K), generator=g), dim=-1).to(torch.bfloat16).to(DEV)
+    sample = deq[:N:64].float()
+    thr = torch.topk(q.float() @ sample.t(), 64, dim=1).values[:, 63].contiguous()
+    cap = 16384
+    v8, i8, c8 = ops.score_candidates_fp8(q, shuf8, exps, N, thr, cap)
+    v16, i16, c16 = ops.score_candidates_shuffled(q, shuf16, N, thr, cap)
+    torch.cuda.synchronize()
+    assert torch.equal(c8, c16)
+    assert int(c8.min()) >= 64 and int(c8.max()) <= cap, (int(c8.min()), int(c8.max()))
+    for m in range(M):
+        c = int(c8[m])
+        o8, o16 = torch.argsort(i8[m, :c]), torch.argsort(i16[m, :c])
+        assert torch.equal(i8[m, :c][o8], i16[m, :c][o16]), m
+        assert torch.equal(v8[m, :c][o8].view(torch.int32), v16[m, :c][o16].view(torch.int32)), m
+        assert bool((v8[m, c:] == float("-inf")).all())
+
+
+def test_fp8_scan_wrapper(unit_rows):
+    shuf8, exps, _, N, _ = unit_rows
+    K = shuf8.shape[1]
+    thr = torch.zeros(97, device=DEV)
+    q = torch.zeros((97, K), dtype=torch.bfloat16, device=DEV)
+    assert ops.fp8_scan_max_m(768) == 96 and ops.fp8_scan_max_m(1024) == 64
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q, shuf8, exps, N, thr, 64)                          # 97 queries
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q[:4], shuf8.view(torch.int8), exps, N, thr, 64)     # dtype of the bytes
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q[:4], shuf8, exps.to(torch.int32), N, thr, 64)      # dtype of the exponents
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q[:4], shuf8, exps[:N - 200], N, thr, 64)            # too few exponents
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q[:4], shuf8[:N - 200 - (N - 200) % 16], exps, N, thr, 64)  # too few rows
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q[:4], shuf8, exps[1:], N - 1, thr, 64)              # misaligned exponents
+    with pytest.raises(ValueError):
+        ops.score_candidates_fp8(q[:4, :640], shuf8[:, :640].contiguous(), exps, N, thr, 64)  # K % 256
+
+
+# ---------------------------------------------------------------------------------------------
+# the dequantiser
+
+
+@pytest.mark.parametrize("K", (256, 768))
+def test_dequant_blocks(K):
+    R = 1040  # 65 blocks
+    g = torch.Generator(device="cpu").manual_seed(K)
+    rows = (torch.randn((R, K), generator=g) * torch.exp(torch.randn((R, 1), generator=g) * 3)).to(torch.bfloat16)
+    data, exps = ops.kv_quantize(rows.to(DEV))
+    want = ops.shuffle_weights(ops.weight_dequantize_fp8(data, exps))
+    shuf = ops.shuffle_weights_fp8(data)
+    nb = R // 16
+    for b0, b1 in ((0, 1), (0, nb), (nb - 1, nb), (3, 17), (7, 7)):
+        out = torch.full((R, K), -7.0, dtype=torch.bfloat16, device=DEV)
+        ops.index_dequant_blocks(shuf, exps, b0, b1, out, b0)
+        torch.cuda.synchronize()
+        assert torch.equal(out[16 * b0:16 * b1].view(torch.int16), want[16 * b0:16 * b1].view(torch.int16)), (b0, b1)
+        assert bool((out[:16 * b0] == -7).all() and (out[16 * b1:] == -7).all()), (b0, b1)
+    # into a smaller scratch at another block offset
+    out = torch.full((64, K), -7.0, dtype=torch.bfloat16, device=DEV)
+    ops.index_dequant_blocks(shuf, exps, nb - 2, nb, out, 1)
+    assert torch.equal(out[16:48].view(torch.int16), want[16 * (nb - 2):].view(torch.int16))
+    assert bool((out[:16] == -7).all() and (out[48:] == -7).all())
+    with pytest.raises(ValueError):
+        ops.index_dequant_blocks(shuf, exps, nb - 2, nb, out, 3)  # would run past the scratch
+    with pytest.raises(ValueError):
+        ops.index_dequant_blocks(shuf, exps, 0, nb + 1, out, 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# VectorIndex end to end
+
+DIM, ROWS = 256, 70_000
+
+
+def _twin(idx: VectorIndex) -> VectorIndex:
+    """A bf16 index that holds the FP8 index's dequantised rows verbatim, with the same metadata."""
+    t = VectorIndex(idx.dim, DEV, capacity=idx._cap, dtype=torch.bfloat16)
+    assert t.frag and t._cap == idx._cap
+    n = idx.n
+    r = torch.arange(n, device=DEV)
+    t._put(r, idx.rows_data(r))
+    t.row_ids[:n], t.row_docs[:n], t.row_group[:n] = idx.row_ids[:n], idx.row_docs[:n], idx.row_group[:n]
+    t.n, t._dead, t._row_of, t._sorted = n, idx._dead, dict(idx._row_of), None
+    t._version += 1
+    t.threshold_min_rows = idx.threshold_min_rows
+    return t
+
+
+@pytest.fixture(scope="module")
+def pair():
+    g = torch.Generator(device="cpu").manual_seed(4321)
+    v = torch.randn((ROWS, DIM), generator=g)
+    ids = np.arange(10, 10 + ROWS, dtype=np.int64)
+    idx = VectorIndex(DIM, DEV, capacity=ROWS, dtype=FP8)
+    assert idx.fp8 and idx.frag8 and idx.vecs.dtype == torch.uint8
+    idx.threshold_min_rows = 1024
+    idx.SCORE_SCRATCH_BYTES = 10240 * DIM * 2  # 7 chunks of 10240 rows, the last one ragged
+    idx.add(ids, v, doc_ids=np.arange(ROWS) // 4, groups=(np.arange(ROWS) % 3).astype(np.int32))
+    q = torch.randn((200, DIM), generator=g)
+    return idx, _twin(idx), q
+
+
+def _same(a, b):
+    (sa, ia, da), (sb, ib, db) = a, b
+    assert sa.shape == sb.shape and torch.equal(sa.view(torch.int32), sb.view(torch.int32))
+    distinct = torch.ones_like(sa, dtype=torch.bool)
+    distinct[:, 1:] &= sa[:, 1:] != sa[:, :-1]
+    distinct[:, :-1] &= sa[:, 1:] != sa[:, :-1]
+    assert torch.equal(ia[distinct], ib[distinct]) and torch.equal(da[distinct], db[distinct])
+    assert int(distinct.sum()) > distinct.numel() // 2
+
+
+def _compare(idx, twin, q):
+    groups = (np.arange(len(q)) % 4 - 1).astype(np.int32)  # -1 (any group), 0, 1, 2
+    for nq in (1, 96, 97, 200):
+        for k in (10, 250):
+            before = idx.stats["threshold_searches"]
+            _same(idx.search(q[:nq], k), twin.search(q[:nq], k))
+            _same(idx.search(q[:nq], k, q_groups=groups[:nq]), twin.search(q[:nq], k, q_groups=groups[:nq]))
+            assert idx.stats["threshold_searches"] == before + 2  # the FP8 scan served both
+    # the score-matrix path (dequantised chunks through the bf16 GEMM)
+    live = idx.row_ids[:idx.n][idx.row_group[:idx.n] >= 0].cpu().numpy()
+    allowed = [set(live[i::5 + i].tolist()) for i in range(7)]
+    _same(idx.search(q[:7], 10, allowed=allowed), twin.search(q[:7], 10, allowed=allowed))
+    lim = [5, 100, 1000, 5000, 17000, 17499, 20000]
+    _same(idx.search(q[:7], 250, doc_lt=lim), twin.search(q[:7], 250, doc_lt=lim))
+    _same(idx.search(q[:7], 10, q_groups=groups[:7], allowed=allowed, doc_lt=lim),
+          twin.search(q[:7], 10, q_groups=groups[:7], allowed=allowed, doc_lt=lim))
+    sa, sb = idx.scores(q[:5]), twin.scores(q[:5])
+    assert sa.shape == sb.shape and torch.equal(sa.view(torch.int32), sb.view(torch.int32))
+
+
+def test_fp8_index_matches_its_bf16_twin(pair):
+    idx, twin, q = pair
+    assert idx.vecs.numel() + idx.exps.numel() == idx._cap * (DIM + 1)  # dim + 1 bytes per row
+    assert -(-idx.n // (idx.SCORE_SCRATCH_BYTES // (2 * DIM))) == 7
+    _compare(idx, twin, q)
+
+
+def test_fp8_index_after_remove_compact_and_growth(pair):
+    idx, _, q = pair
+    ids = np.arange(10, 10 + ROWS, dtype=np.int64)
+    assert idx.remove(ids[5::7]) == len(ids[5::7])
+    live = (idx.row_group[:idx.n] >= 0).nonzero().flatten()
+    want = idx._rows_fp8(live)
+    idx.compact()
+    assert idx.n == len(live) == len(idx)
+    got = idx._rows_fp8(torch.arange(idx.n, device=DEV))
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])  # bytes and exponents moved as they were
+    _compare(idx, _twin(idx), q)
+    # an upsert (some existing ids, many new ones) that grows the index past its capacity
+    cap = idx._cap
+    g = torch.Generator(device="cpu").manual_seed(777)
+    n_new = cap - idx.n + 3000
+    new_ids = np.concatenate([ids[:500], np.arange(10 ** 6, 10 ** 6 + n_new, dtype=np.int64)])
+    idx.add(new_ids, torch.randn((len(new_ids), DIM), generator=g), doc_ids=np.arange(len(new_ids)),
+            groups=(np.arange(len(new_ids)) % 3).astype(np.int32))
+    assert idx._cap > cap
+    _compare(idx, _twin(idx), q)
+
+
+def test_fp8_index_snapshot_round_trip(pair, tmp_path):
+    idx, _, q = pair
+    path = str(tmp_path / "fp8.safetensors")
+    idx.save(path)
+    back = VectorIndex.load(path, DEV)
+    assert back.frag8 and back.n == idx.n
+    assert torch.equal(back.vecs.view(-1)[: idx.n // 16 * 16 * DIM], idx.vecs.view(-1)[: idx.n // 16 * 16 * DIM])
+    assert torch.equal(back.exps[:idx.n], idx.exps[:idx.n])
+    back.threshold_min_rows = idx.threshold_min_rows
+    _same(back.search(q[:9], 10), idx.search(q[:9], 10))
+
+
+def test_fp8_index_widths_on_the_gpu():
+    for dim in (128, 384, 1280):
+        with pytest.raises(ValueError):
+            VectorIndex(dim, DEV, dtype=FP8)
+    assert VectorIndex(1024, DEV, dtype="fp8").frag8

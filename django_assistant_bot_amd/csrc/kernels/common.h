@@ -131,6 +131,17 @@ __device__ __forceinline__ bf16x8 fp8x8_bf16(uint32_t lo, uint32_t hi) {
 
 __device__ __forceinline__ float exp_scale(uint32_t b) { return __uint_as_float(b << 23); }  // 2^(b - 127)
 
+// 16 e4m3fn bytes times the row's scale `s` (exp_scale) -> 16 bf16 in byte order: o[0] bytes 0 - 7,
+// o[1] bytes 8 - 15 (the dequantisers of the KV cache and of the index)
+__device__ __forceinline__ void fp8x16_dequant(const u32x4& d, float s, u32x4 (&o)[2]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(d[q], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(d[q], true);
+    o[q >> 1][2 * (q & 1)] = pack2bf(lo[0] * s, lo[1] * s);
+    o[q >> 1][2 * (q & 1) + 1] = pack2bf(hi[0] * s, hi[1] * s);
+  }
+}
+
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 // ds_read_b64_tr_b16: per 16-lane group, lane 4q+p supplies the address of row q, columns 4p..4p+3

@@ -23,14 +23,22 @@
 //     (ops.shuffle_weights), where each 16-row x 32-k A fragment is 1 KB contiguous in lane order:
 //     every load is one fully coalesced 1 KB read instead of 16 rows x 64 B.
 //
-// FP8 rows (index_scan_fp8_kernel, the opt-in FP8 index): the same scan over e4m3fn bytes in the
+// One kernel, index_scan_kernel<FMT, MT, NW, NWIN>, over the three row formats (ScanFmt): the
+// candidate lists, the query staging, the tile walk and the hit epilogue are written once, and what
+// a format changes (ring slot type and chunk width, the descriptors, the exponent loads, the MFMA
+// feed, the score's scale) sits behind `if constexpr`.
+//
+// FP8 rows (kScanFp8, the opt-in FP8 index): the same scan over e4m3fn bytes in the
 // ops.shuffle_weights_fp8 layout [rows/16][K/64][64 lanes][16 B] with one E8M0 exponent byte per row.
 // A ring slot is one 16-row x 64-k fragment per A tile (16 B per lane, still one coalesced 1 KB
-// read); it is converted in registers (fp8x8_bf16) into the two bf16 A fragments the bf16 kernel
-// would have loaded and fed to the same MFMA sequence in the same k order, and the row's exponent
-// scales the fp32 sum before the threshold test: the scores are bit-identical to the bf16 scan over
-// the dequantised rows.  index_dequant_kernel turns 16-row blocks of that copy into the bf16
-// fragment layout for the callers that need a full score matrix.
+// read; NWIN of them in flight per wave, NWIN divides K / 64); it is converted in registers
+// (fp8x8_bf16) into the two bf16 A fragments the bf16 arm would have loaded and fed to the same MFMA
+// sequence in the same k order, and the row's exponent scales the fp32 sum before the threshold
+// test: the scores are bit-identical to the bf16 scan over the dequantised rows.
+// index_dequant_kernel turns 16-row blocks of that copy into the bf16 fragment layout for the
+// callers that need a full score matrix (fp8x16_dequant, common.h).
+#include <type_traits>
+
 #include "common.h"
 #include "launchers.h"
 
@@ -59,14 +67,22 @@ constexpr int kScanMaxM = 96;
 // widest rows the queries of MT 16-query tiles may have (LDS: 16 MT KMax 2 B <= 144 KB)
 constexpr int scan_kmax(int mt) { return mt <= 4 ? kScanKMax : 768; }
 constexpr int kScanRT = 2;     // 16-row A tiles per wave
-constexpr int kScanNWIN = 8;   // chunks (of 32 k) in flight per wave
+constexpr int kScanNWIN = 8;   // bf16 rows: chunks (of 32 k) in flight per wave
 constexpr int kScanListW = 160;  // candidate list entries per wave (12 B each)
+
+// the rows: row-major bf16 [N, ldw]; bf16 fragments (shuffle_weights); e4m3fn fragments with one
+// exponent byte per row (shuffle_weights_fp8)
+enum ScanFmt { kScanRows, kScanShuf, kScanFp8 };
 
 }  // namespace
 
-template <bool SHUF, int MT, int NW>
+// NWIN: ring depth in chunks (kScanNWIN for bf16 rows; FP8: divides K / 64, see index_scan_candidates_fp8)
+template <ScanFmt FMT, int MT, int NW, int NWIN>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_kernel(ScanParams p) {
-  constexpr int RT = kScanRT, NWIN = kScanNWIN, TR = 32 * NW;  // rows per workgroup tile
+  constexpr bool SHUF = FMT != kScanRows, FP8 = FMT == kScanFp8;
+  static_assert(FP8 || NWIN == kScanNWIN, "bf16 rows: the launchers check K against a ring of kScanNWIN chunks");
+  constexpr int CK = FP8 ? 64 : 32;          // k per ring chunk: 16 B per lane and A tile
+  constexpr int RT = kScanRT, TR = 32 * NW;  // rows per workgroup tile
   constexpr int XS = 16 * MT * scan_kmax(MT) * 2;
   __shared__ __attribute__((aligned(16))) char xs[XS + 64 + NW * kScanListW * 12];
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
@@ -120,21 +136,23 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_kernel(ScanParams 
   __syncthreads();
 
   // ---- flat chunk stream over this wave's tiles: tile i of the wave = rows
-  // (blockIdx.x + i * gridDim.x) * TR + 32 w .. + 31; chunk = 32 k of both 16-row A tiles
-  const int nck = p.K / 32;  // chunks per tile (a multiple of NWIN: checked by the launcher)
+  // (blockIdx.x + i * gridDim.x) * TR + 32 w .. + 31; chunk = CK k of both 16-row A tiles
+  const int nck = p.K / CK;  // chunks per tile (a multiple of NWIN: checked by the launcher)
   const int tiles = (p.N + TR - 1) / TR;
   const int my_tiles = blockIdx.x < tiles ? (tiles - 1 - blockIdx.x) / gridDim.x + 1 : 0;
   if (my_tiles == 0) return;
   auto tile_row0 = [&](int i) { return (blockIdx.x + i * gridDim.x) * TR + 32 * w; };
   // descriptor of tile i (rows past N read zeros); past the wave's last tile or wholly past N: empty
   // range (the ring's loads return zeros without memory traffic)
-  // SHUF: a tile's two 16-row blocks are whole in the copy (round_up(N, 128) rows) when it starts
-  // below N; rows >= N there score like any row and are dropped by the epilogue's n < N test
+  // SHUF: a chunk of a 16-row block is 1 KB in both fragment layouts ([blk][K / CK][64 lanes][16 B]);
+  // a tile's two blocks are whole in the copy (round_up(N, 128) rows) when it starts below N; rows
+  // >= N there score like any row and are dropped by the epilogue's n < N test
   auto rsrc_of = [&](int i) {
     const int r0 = tile_row0(i);
     const bool live = i < my_tiles && r0 < p.N;
     if constexpr (SHUF) {
-      return __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (size_t)(min(r0, p.N - 1) / 16) * nck * 512), (short)0,
+      const char* const blocks = reinterpret_cast<const char*>(p.W);
+      return __builtin_amdgcn_make_buffer_rsrc((void*)(blocks + (size_t)(min(r0, p.N - 1) / 16) * nck * 1024), (short)0,
                                                live ? 2 * nck * 1024 : 0, 0x00020000);
     } else {
       const int rows = live ? min(32, p.N - r0) : 0;
@@ -142,18 +160,35 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_kernel(ScanParams 
                                                (int)(rows * p.ldw * 2), 0x00020000);
     }
   };
+  // FP8 (unused otherwise): the exponent bytes of rows 4 g .. + 3 of each A tile: one dword per tile
+  // and lane.  Range: the whole dwords that hold a row < N (a tile past N reads zeros; its scores
+  // are dropped)
+  [[maybe_unused]] const auto ex_rs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)p.exps, (short)0, (p.N + 3) / 4 * 4, 0x00020000);
   const int voff = SHUF ? lane * 16 : (int)((li * p.ldw + 8 * g) * 2);
   const int astr = SHUF ? nck * 1024 : (int)(16 * p.ldw * 2);  // next 16-row block
-  constexpr int CSTR = SHUF ? 1024 : 64;                         // next 32-k chunk
+  constexpr int CSTR = SHUF ? 1024 : 64;                         // next chunk
 
-  bf16x8 wr[NWIN][RT];
+  // a ring slot: one bf16 A fragment (32 k), or the 16 FP8 bytes of two (64 k)
+  using slot_t = std::conditional_t<FP8, u32x4, bf16x8>;
+  slot_t wr[NWIN][RT];
+  [[maybe_unused]] uint32_t ex_ld[RT];  // exponents of the tile whose chunks are being loaded
   int ld_tile = 0, ld_c = 0;  // next chunk to load (wave-uniform)
   auto ld_rs = rsrc_of(0);
   auto load = [&](int slot) __attribute__((always_inline)) {
+    if constexpr (FP8) {
+      // slot 0 carries the exponents of its chunk's tile: no branch in the ring, and they arrive
+      // with the tile's first chunk (ld_c % NWIN == slot, so chunk 0 of a tile is always slot 0's)
+      if (slot == 0) {
+        const int e0 = tile_row0(ld_tile) + 4 * g;
+#pragma unroll
+        for (int a = 0; a < RT; ++a) ex_ld[a] = __builtin_amdgcn_raw_buffer_load_b32(ex_rs, e0 + 16 * a, 0, 0);
+      }
+    }
 #pragma unroll
     for (int a = 0; a < RT; ++a)
       wr[slot][a] = __builtin_bit_cast(
-          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ld_rs, voff + a * astr, ld_c * CSTR, 2));  // nt: read once
+          slot_t, __builtin_amdgcn_raw_buffer_load_b128(ld_rs, voff + a * astr, ld_c * CSTR, 2));  // nt: read once
     if (++ld_c == nck) {
       ld_c = 0;
       ld_rs = rsrc_of(++ld_tile);
@@ -168,169 +203,26 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_kernel(ScanParams 
     for (int a = 0; a < RT; ++a)
 #pragma unroll
       for (int t = 0; t < MT; ++t) acc[a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int c0 = 0; c0 < nck; c0 += NWIN) {
+    [[maybe_unused]] uint32_t ex[RT];  // this tile's exponents (ex_ld moves on to the next tile during the loop)
+    if constexpr (FP8) {
 #pragma unroll
-      for (int s = 0; s < NWIN; ++s) {
-        const int c = c0 + s;
-        bf16x8 bx[MT];
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-          bx[t] = *reinterpret_cast<const bf16x8*>(xs + (16 * t + li) * RB + 16 * ((4 * c + g) ^ li));
-#pragma unroll
-        for (int a = 0; a < RT; ++a)
-#pragma unroll
-          for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wr[s][a], bx[t], acc[a][t]);
-        load(s);  // refill the slot right behind its MFMAs (NWIN chunks ahead)
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // ---- candidates: acc[a][t] lane (li, g) = scores of query 16 t + li against rows 16 a + 4 g + r
-    const int r0 = tile_row0(i);
-    if (r0 >= p.N) continue;  // wave-uniform
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int a = 0; a < RT; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int n = r0 + 16 * a + 4 * g + r;
-          const float v = acc[a][t][r];
-          const bool hit = v >= thr[t] && n < p.N;
-          // the list holds <= kScanListW - 64 entries here, so the <= 64 hits of one step fit
-          if (__builtin_amdgcn_ballot_w64(hit)) {
-            if (hit) {
-              const int slot = __hip_atomic_fetch_add(lcnt + w, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              l_n[slot] = n;
-              l_m[slot] = 16 * t + li;
-              l_v[slot] = v;
-            }
-            if (list_count() > kScanListW - 64) cand_flush();
-          }
-        }
-  }
-  cand_flush();
-}
-
-// The FP8 arm: index_scan_kernel<SHUF = true> with 16-B FP8 ring slots (NWIN chunks of 64 k in
-// flight per wave; NWIN divides K / 64) and the rows' exponents in the epilogue.
-template <int MT, int NW, int NWIN>
-__global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_fp8_kernel(ScanParams p) {
-  constexpr int RT = kScanRT, TR = 32 * NW;  // rows per workgroup tile
-  constexpr int XS = 16 * MT * scan_kmax(MT) * 2;
-  __shared__ __attribute__((aligned(16))) char xs[XS + 64 + NW * kScanListW * 12];
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cpr = p.K / 8;  // 16-B chunks per query row
-  const int RB = p.K * 2;
-
-  // ---- per-wave candidate lists: as in index_scan_kernel
-  int* const lcnt = reinterpret_cast<int*>(xs + XS);
-  int* const l_n = lcnt + 16 + w * kScanListW;
-  int* const l_m = lcnt + 16 + NW * kScanListW + w * kScanListW;
-  float* const l_v = reinterpret_cast<float*>(lcnt + 16 + 2 * NW * kScanListW + w * kScanListW);
-  auto cand_global = [&](int m, int n, float v) {
-    const int rg = p.row_group ? p.row_group[n] : 0;
-    const int qgm = p.q_group ? p.q_group[m] : -1;
-    if (rg >= 0 && (qgm < 0 || rg == qgm)) {
-      const int slot = atomicAdd(p.cnt + m, 1);
-      if (slot < p.cap) {
-        p.cand_val[(size_t)m * p.cap + slot] = v;
-        p.cand_idx[(size_t)m * p.cap + slot] = n;
-      }
-    }
-  };
-  auto list_count = [&]() {
-    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(lcnt + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-  };
-  auto cand_flush = [&]() {  // wave-uniform
-    const int c = list_count();
-    for (int e = lane; e < c; e += 64) cand_global(l_m[e], l_n[e], l_v[e]);
-    if (lane == 0) __hip_atomic_store(lcnt + w, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): see index_scan_kernel
-  };
-  if (tid < NW) lcnt[tid] = 0;
-
-  // ---- queries -> LDS once (rows >= M repeat row M - 1; their scores are never appended)
-  for (int e = tid; e < 16 * MT * cpr; e += 64 * NW) {
-    const int r = e / cpr, c = e % cpr;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(p.X + (size_t)min(r, p.M - 1) * p.ldx + 8 * c);
-    *reinterpret_cast<u32x4*>(xs + r * RB + 16 * (c ^ (r & 15))) = v;
-  }
-  float thr[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const int m = 16 * t + li;
-    thr[t] = m < p.M ? p.thr[m] : __builtin_huge_valf();
-  }
-  __syncthreads();
-
-  // ---- flat chunk stream over this wave's tiles (tile i = rows (blockIdx.x + i gridDim.x) TR + 32 w
-  // .. + 31); chunk = 64 k of both 16-row A tiles: 1 KB each, [blk][K / 64][64 lanes][16 B]
-  const int nck = p.K / 64;  // chunks per tile (a multiple of NWIN: checked by the launcher)
-  const int tiles = (p.N + TR - 1) / TR;
-  const int my_tiles = blockIdx.x < tiles ? (tiles - 1 - blockIdx.x) / gridDim.x + 1 : 0;
-  if (my_tiles == 0) return;
-  auto tile_row0 = [&](int i) { return (blockIdx.x + i * gridDim.x) * TR + 32 * w; };
-  // a tile's two 16-row blocks are whole in the copy (round_up(N, 128) rows) when it starts below N;
-  // past the wave's last tile or wholly past N: empty range (loads return zeros without traffic)
-  const uint8_t* const W8 = reinterpret_cast<const uint8_t*>(p.W);
-  auto rsrc_of = [&](int i) {
-    const int r0 = tile_row0(i);
-    const bool live = i < my_tiles && r0 < p.N;
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(W8 + (size_t)(min(r0, p.N - 1) / 16) * nck * 1024), (short)0,
-                                             live ? 2 * nck * 1024 : 0, 0x00020000);
-  };
-  // the exponent bytes of rows 4 g .. + 3 of each A tile: one dword per tile and lane.  Range: the
-  // whole dwords that hold a row < N (a tile past N reads zeros; its scores are dropped)
-  const auto ex_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.exps, (short)0, (p.N + 3) / 4 * 4, 0x00020000);
-  const int voff = lane * 16;
-  const int astr = nck * 1024;  // next 16-row block
-
-  u32x4 wr[NWIN][RT];
-  uint32_t ex_ld[RT];  // exponents of the tile whose chunks are being loaded
-  int ld_tile = 0, ld_c = 0;  // next chunk to load (wave-uniform)
-  auto ld_rs = rsrc_of(0);
-  auto load = [&](int slot) __attribute__((always_inline)) {
-    // slot 0 carries the exponents of its chunk's tile: no branch in the ring, and they arrive
-    // with the tile's first chunk (ld_c % NWIN == slot, so chunk 0 of a tile is always slot 0's)
-    if (slot == 0) {
-      const int e0 = tile_row0(ld_tile) + 4 * g;
-#pragma unroll
-      for (int a = 0; a < RT; ++a) ex_ld[a] = __builtin_amdgcn_raw_buffer_load_b32(ex_rs, e0 + 16 * a, 0, 0);
-    }
-#pragma unroll
-    for (int a = 0; a < RT; ++a)
-      wr[slot][a] = __builtin_amdgcn_raw_buffer_load_b128(ld_rs, voff + a * astr, ld_c * 1024, 2);  // nt: read once
-    if (++ld_c == nck) {
-      ld_c = 0;
-      ld_rs = rsrc_of(++ld_tile);
-    }
-  };
-#pragma unroll
-  for (int s = 0; s < NWIN; ++s) load(s);
-
-  f32x4 acc[RT][MT];
-  for (int i = 0; i < my_tiles; ++i) {
-    uint32_t ex[RT];  // this tile's exponents (ex_ld moves on to the next tile during the loop)
-#pragma unroll
-    for (int a = 0; a < RT; ++a) {
-      ex[a] = ex_ld[a];
-#pragma unroll
-      for (int t = 0; t < MT; ++t) acc[a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int a = 0; a < RT; ++a) ex[a] = ex_ld[a];
     }
     for (int c0 = 0; c0 < nck; c0 += NWIN) {
 #pragma unroll
       for (int s = 0; s < NWIN; ++s) {
         const int c = c0 + s;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {  // the 64-k fragment's two 32-k halves, in k order
+        for (int h = 0; h < CK / 32; ++h) {  // the chunk's 32-k halves (FP8: two), in k order
           bf16x8 bx[MT];
 #pragma unroll
           for (int t = 0; t < MT; ++t)
-            bx[t] = *reinterpret_cast<const bf16x8*>(xs + (16 * t + li) * RB + 16 * ((4 * (2 * c + h) + g) ^ li));
+            bx[t] = *reinterpret_cast<const bf16x8*>(xs + (16 * t + li) * RB + 16 * ((4 * (CK / 32 * c + h) + g) ^ li));
 #pragma unroll
           for (int a = 0; a < RT; ++a) {
-            const bf16x8 wa = fp8x8_bf16(wr[s][a][2 * h], wr[s][a][2 * h + 1]);
+            bf16x8 wa;
+            if constexpr (FP8) wa = fp8x8_bf16(wr[s][a][2 * h], wr[s][a][2 * h + 1]);
+            else wa = wr[s][a];
 #pragma unroll
             for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wa, bx[t], acc[a][t]);
           }
@@ -339,15 +231,17 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_fp8_kernel(ScanPar
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    // ---- candidates: acc[a][t] lane (li, g) = unscaled scores of query 16 t + li against rows
-    // 16 a + 4 g + r; score = acc x 2^(exponent byte - 127)
+    // ---- candidates: acc[a][t] lane (li, g) = scores of query 16 t + li against rows 16 a + 4 g + r
+    // (FP8: unscaled; score = acc x 2^(exponent byte - 127))
     const int r0 = tile_row0(i);
     if (r0 >= p.N) continue;  // wave-uniform
-    float sc[RT][4];
+    [[maybe_unused]] float sc[RT][4];
+    if constexpr (FP8) {
 #pragma unroll
-    for (int a = 0; a < RT; ++a)
+      for (int a = 0; a < RT; ++a)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sc[a][r] = exp_scale((ex[a] >> (8 * r)) & 0xffu);
+        for (int r = 0; r < 4; ++r) sc[a][r] = exp_scale((ex[a] >> (8 * r)) & 0xffu);
+    }
 #pragma unroll
     for (int t = 0; t < MT; ++t)
 #pragma unroll
@@ -355,7 +249,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void index_scan_fp8_kernel(ScanPar
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = r0 + 16 * a + 4 * g + r;
-          const float v = acc[a][t][r] * sc[a][r];
+          float v = acc[a][t][r];
+          if constexpr (FP8) v *= sc[a][r];
           const bool hit = v >= thr[t] && n < p.N;
           // the list holds <= kScanListW - 64 entries here, so the <= 64 hits of one step fit
           if (__builtin_amdgcn_ballot_w64(hit)) {
@@ -381,96 +276,23 @@ __global__ __launch_bounds__(256) void index_dequant_kernel(const uint8_t* __res
     const int lane = (int)(i & 63);
     const size_t f = i >> 6, blk = f / nck, j = f - blk * nck;  // blk: relative to b0
     const u32x4 d = *reinterpret_cast<const u32x4*>(data + (((b0 + blk) * nck + j) * 64 + lane) * 16);
-    const float s = exp_scale(exps[(b0 + blk) * 16 + (lane & 15)]);
     u32x4 o[2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(d[q], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(d[q], true);
-      o[q >> 1][2 * (q & 1)] = pack2bf(lo[0] * s, lo[1] * s);
-      o[q >> 1][2 * (q & 1) + 1] = pack2bf(hi[0] * s, hi[1] * s);
-    }
+    fp8x16_dequant(d, exp_scale(exps[(b0 + blk) * 16 + (lane & 15)]), o);
     bf16* dst = out + (((ob + blk) * 2 * nck + 2 * j) * 64 + lane) * 8;
     *reinterpret_cast<u32x4*>(dst) = o[0];
     *reinterpret_cast<u32x4*>(dst + 512) = o[1];
   }
 }
 
-static int index_scan_launch(bool shuf, const void* X, long ldx, const void* W, long ldw, int M, int N, int K,
-                             const int* row_group, const int* q_group, const float* thr, int* cnt, float* cand_val,
-                             int* cand_idx, int cap, hipStream_t s) {
+// exps / nwin: FP8 rows only (else nullptr / kScanNWIN)
+static int index_scan_launch(ScanFmt fmt, int nwin, const void* X, long ldx, const void* W, long ldw, const void* exps,
+                             int M, int N, int K, const int* row_group, const int* q_group, const float* thr, int* cnt,
+                             float* cand_val, int* cand_idx, int cap, hipStream_t s) {
   ScanParams p;
   p.X = (const bf16*)X;
   p.ldx = ldx;
   p.W = (const bf16*)W;
   p.ldw = ldw;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.row_group = row_group;
-  p.q_group = q_group;
-  p.thr = thr;
-  p.cnt = cnt;
-  p.cand_val = cand_val;
-  p.cand_idx = cand_idx;
-  p.cap = cap;
-  p.exps = nullptr;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int mt = (M + 15) / 16;
-  const int nw = mt <= 2 ? 4 : 8, per_cu = 8 / nw;
-  const long tiles = (N + 32L * nw - 1) / (32L * nw);
-  const int grid = (int)(tiles < (long)per_cu * cus ? tiles : (long)per_cu * cus);
-#define SCAN_LAUNCH(MT_, NW_)                                                                        \
-  do {                                                                                               \
-    if (shuf) hipLaunchKernelGGL((index_scan_kernel<true, MT_, NW_>), dim3(grid), dim3(64 * NW_), 0, s, p); \
-    else hipLaunchKernelGGL((index_scan_kernel<false, MT_, NW_>), dim3(grid), dim3(64 * NW_), 0, s, p);     \
-  } while (0)
-  switch (mt) {
-    case 1: SCAN_LAUNCH(1, 4); break;
-    case 2: SCAN_LAUNCH(2, 4); break;
-    case 3: SCAN_LAUNCH(3, 8); break;
-    case 4: SCAN_LAUNCH(4, 8); break;
-    case 5: SCAN_LAUNCH(5, 8); break;
-    default: SCAN_LAUNCH(6, 8); break;
-  }
-#undef SCAN_LAUNCH
-  return hipGetLastError();
-}
-
-int index_scan_candidates(const void* X, long ldx, const void* W, long ldw, int M, int N, int K, const int* row_group,
-                          const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx, int cap,
-                          hipStream_t s) {
-  if (M <= 0 || N <= 0) return 0;
-  if (M > kScanMaxM || K > scan_kmax((M + 15) / 16) || K % (32 * kScanNWIN) || ldx % 8 || ldw % 8 || cap <= 0)
-    return hipErrorInvalidValue;
-  if (32L * ldw * 2 >= (1L << 31)) return hipErrorInvalidValue;
-  return index_scan_launch(false, X, ldx, W, ldw, M, N, K, row_group, q_group, thr, cnt, cand_val, cand_idx, cap, s);
-}
-
-// W: the rows in the shuffle_weights layout, with at least round_up(N, 32) rows
-int index_scan_candidates_shuf(const void* X, long ldx, const void* W, int M, int N, int K, const int* row_group,
-                               const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx,
-                               int cap, hipStream_t s) {
-  if (M <= 0 || N <= 0) return 0;
-  if (M > kScanMaxM || K > scan_kmax((M + 15) / 16) || K % (32 * kScanNWIN) || ldx % 8 || cap <= 0)
-    return hipErrorInvalidValue;
-  return index_scan_launch(true, X, ldx, W, K, M, N, K, row_group, q_group, thr, cnt, cand_val, cand_idx, cap, s);
-}
-
-// W: e4m3fn bytes in the shuffle_weights_fp8 layout with at least round_up(N, 32) rows; exps: one
-// exponent byte per row, 4-byte aligned, at least round_up(N, 4) of them
-int index_scan_candidates_fp8(const void* X, long ldx, const void* W, const void* exps, int M, int N, int K,
-                              const int* row_group, const int* q_group, const float* thr, int* cnt, float* cand_val,
-                              int* cand_idx, int cap, hipStream_t s) {
-  if (M <= 0 || N <= 0) return 0;
-  if (M > kScanMaxM || K > scan_kmax((M + 15) / 16) || K % 256 || ldx % 8 || cap <= 0 || !exps ||
-      (reinterpret_cast<uintptr_t>(exps) & 3))
-    return hipErrorInvalidValue;
-  ScanParams p;
-  p.X = (const bf16*)X;
-  p.ldx = ldx;
-  p.W = (const bf16*)W;
-  p.ldw = K;
   p.M = M;
   p.N = N;
   p.K = K;
@@ -488,24 +310,64 @@ int index_scan_candidates_fp8(const void* X, long ldx, const void* W, const void
   const int nw = mt <= 2 ? 4 : 8, per_cu = 8 / nw;
   const long tiles = (N + 32L * nw - 1) / (32L * nw);
   const int grid = (int)(tiles < (long)per_cu * cus ? tiles : (long)per_cu * cus);
-  // ring depth in 64-k chunks: the deepest of 8 / 6 / 4 that divides K / 64 (K % 256 == 0: 4 always does)
-  const int nck = K / 64, nwin = nck % 8 == 0 ? 8 : nck % 6 == 0 ? 6 : 4;
-#define SCAN8_LAUNCH(MT_, NW_)                                                                               \
-  do {                                                                                                       \
-    if (nwin == 8) hipLaunchKernelGGL((index_scan_fp8_kernel<MT_, NW_, 8>), dim3(grid), dim3(64 * NW_), 0, s, p); \
-    else if (nwin == 6) hipLaunchKernelGGL((index_scan_fp8_kernel<MT_, NW_, 6>), dim3(grid), dim3(64 * NW_), 0, s, p); \
-    else hipLaunchKernelGGL((index_scan_fp8_kernel<MT_, NW_, 4>), dim3(grid), dim3(64 * NW_), 0, s, p);      \
+#define SCAN_KERNEL(FMT_, MT_, NW_, NWIN_) \
+  hipLaunchKernelGGL((index_scan_kernel<FMT_, MT_, NW_, NWIN_>), dim3(grid), dim3(64 * NW_), 0, s, p)
+#define SCAN_LAUNCH(MT_, NW_)                                                     \
+  do {                                                                            \
+    if (fmt == kScanRows) SCAN_KERNEL(kScanRows, MT_, NW_, kScanNWIN);            \
+    else if (fmt == kScanShuf) SCAN_KERNEL(kScanShuf, MT_, NW_, kScanNWIN);       \
+    else if (nwin == 8) SCAN_KERNEL(kScanFp8, MT_, NW_, 8);                       \
+    else if (nwin == 6) SCAN_KERNEL(kScanFp8, MT_, NW_, 6);                       \
+    else SCAN_KERNEL(kScanFp8, MT_, NW_, 4);                                      \
   } while (0)
   switch (mt) {
-    case 1: SCAN8_LAUNCH(1, 4); break;
-    case 2: SCAN8_LAUNCH(2, 4); break;
-    case 3: SCAN8_LAUNCH(3, 8); break;
-    case 4: SCAN8_LAUNCH(4, 8); break;
-    case 5: SCAN8_LAUNCH(5, 8); break;
-    default: SCAN8_LAUNCH(6, 8); break;
+    case 1: SCAN_LAUNCH(1, 4); break;
+    case 2: SCAN_LAUNCH(2, 4); break;
+    case 3: SCAN_LAUNCH(3, 8); break;
+    case 4: SCAN_LAUNCH(4, 8); break;
+    case 5: SCAN_LAUNCH(5, 8); break;
+    default: SCAN_LAUNCH(6, 8); break;
   }
-#undef SCAN8_LAUNCH
+#undef SCAN_LAUNCH
+#undef SCAN_KERNEL
   return hipGetLastError();
+}
+
+int index_scan_candidates(const void* X, long ldx, const void* W, long ldw, int M, int N, int K, const int* row_group,
+                          const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx, int cap,
+                          hipStream_t s) {
+  if (M <= 0 || N <= 0) return 0;
+  if (M > kScanMaxM || K > scan_kmax((M + 15) / 16) || K % (32 * kScanNWIN) || ldx % 8 || ldw % 8 || cap <= 0)
+    return hipErrorInvalidValue;
+  if (32L * ldw * 2 >= (1L << 31)) return hipErrorInvalidValue;
+  return index_scan_launch(kScanRows, kScanNWIN, X, ldx, W, ldw, nullptr, M, N, K, row_group, q_group, thr, cnt,
+                           cand_val, cand_idx, cap, s);
+}
+
+// W: the rows in the shuffle_weights layout, with at least round_up(N, 32) rows
+int index_scan_candidates_shuf(const void* X, long ldx, const void* W, int M, int N, int K, const int* row_group,
+                               const int* q_group, const float* thr, int* cnt, float* cand_val, int* cand_idx,
+                               int cap, hipStream_t s) {
+  if (M <= 0 || N <= 0) return 0;
+  if (M > kScanMaxM || K > scan_kmax((M + 15) / 16) || K % (32 * kScanNWIN) || ldx % 8 || cap <= 0)
+    return hipErrorInvalidValue;
+  return index_scan_launch(kScanShuf, kScanNWIN, X, ldx, W, K, nullptr, M, N, K, row_group, q_group, thr, cnt,
+                           cand_val, cand_idx, cap, s);
+}
+
+// W: e4m3fn bytes in the shuffle_weights_fp8 layout with at least round_up(N, 32) rows; exps: one
+// exponent byte per row, 4-byte aligned, at least round_up(N, 4) of them
+int index_scan_candidates_fp8(const void* X, long ldx, const void* W, const void* exps, int M, int N, int K,
+                              const int* row_group, const int* q_group, const float* thr, int* cnt, float* cand_val,
+                              int* cand_idx, int cap, hipStream_t s) {
+  if (M <= 0 || N <= 0) return 0;
+  if (M > kScanMaxM || K > scan_kmax((M + 15) / 16) || K % 256 || ldx % 8 || cap <= 0 || !exps ||
+      (reinterpret_cast<uintptr_t>(exps) & 3))
+    return hipErrorInvalidValue;
+  // ring depth in 64-k chunks: the deepest of 8 / 6 / 4 that divides K / 64 (K % 256 == 0: 4 always does)
+  const int nck = K / 64, nwin = nck % 8 == 0 ? 8 : nck % 6 == 0 ? 6 : 4;
+  return index_scan_launch(kScanFp8, nwin, X, ldx, W, K, exps, M, N, K, row_group, q_group, thr, cnt, cand_val,
+                           cand_idx, cap, s);
 }
 
 // 16-row blocks [b0, b1) of an FP8 fragment copy ([R, K] bytes, exps [R]) -> bf16 fragments, blocks

@@ -2,7 +2,8 @@
 // exponent byte b (value = byte x 2^(b - 127)), K and V alike.
 //
 //   rope_kv_fp8_kernel      : RoPE + quantising cache write (the FP8 form of rope_kv_kernel)
-//   kv_fp8_dequant_kernel   : bf16 image of a list of blocks (the prefill attention reads a scratch)
+//   kv_fp8_dequant_kernel   : bf16 image of a list of blocks (the prefill attention reads a scratch;
+//                             fp8x16_dequant of common.h, as the index's dequantiser)
 //   paged_decode_fp8_kernel : paged_decode_kernel's structure on 128-byte rows, FP8 -> bf16 in
 //                             registers (exact), bf16 MFMA with fp32 accumulation
 //
@@ -122,17 +123,9 @@ __global__ __launch_bounds__(256) void kv_fp8_dequant_kernel(const uint8_t* __re
     const size_t srow = (size_t)ids[ob] * rows_per_block + (orow - ob * rows_per_block);
     const u32x4 kd = *reinterpret_cast<const u32x4*>(k_data + srow * 128 + 16 * c);
     const u32x4 vd = *reinterpret_cast<const u32x4*>(v_data + srow * 128 + 16 * c);
-    const float ks = exp_scale(k_exp[srow]), vs = exp_scale(v_exp[srow]);
     u32x4 ko[2], vo[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2_t k0 = __builtin_amdgcn_cvt_pk_f32_fp8(kd[j], false), k1 = __builtin_amdgcn_cvt_pk_f32_fp8(kd[j], true);
-      const f32x2_t v0 = __builtin_amdgcn_cvt_pk_f32_fp8(vd[j], false), v1 = __builtin_amdgcn_cvt_pk_f32_fp8(vd[j], true);
-      ko[j >> 1][2 * (j & 1)] = pack2bf(k0[0] * ks, k0[1] * ks);
-      ko[j >> 1][2 * (j & 1) + 1] = pack2bf(k1[0] * ks, k1[1] * ks);
-      vo[j >> 1][2 * (j & 1)] = pack2bf(v0[0] * vs, v0[1] * vs);
-      vo[j >> 1][2 * (j & 1) + 1] = pack2bf(v1[0] * vs, v1[1] * vs);
-    }
+    fp8x16_dequant(kd, exp_scale(k_exp[srow]), ko);
+    fp8x16_dequant(vd, exp_scale(v_exp[srow]), vo);
     u32x4* kp = reinterpret_cast<u32x4*>(k_out + orow * 128 + 16 * c);
     u32x4* vp = reinterpret_cast<u32x4*>(v_out + orow * 128 + 16 * c);
     kp[0] = ko[0];

@@ -1,4 +1,4 @@
-"""Cases for the FP8 vector index (``index_scan_fp8_kernel``, ``index_dequant_kernel``, ``VectorIndex`` with
+"""Cases for the FP8 vector index (``index_scan_kernel<kScanFp8, ...>``, ``index_dequant_kernel``, ``VectorIndex`` with
 ``dtype=torch.float8_e4m3fn``): the exact operands of tests/cand_cases.py with a per-row power-of-two scale, the
 defect emulations of the checker's self-test, and the guarded launch of the FP8 scan.  Pure NumPy / torch-CPU but for
 ``launch``; tests/test_index_fp8_cpu.py proves the construction, tests/test_index_fp8_gpu.py uses it on the kernels.

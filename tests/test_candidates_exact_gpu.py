@@ -13,7 +13,7 @@ tests/test_candidates_exact_cpu.py proves the oracle and shows that the checker 
 Kernel instantiation per case, read from ``gemm_score_candidates`` (gemm.hip), the ``score_candidates_shuf``
 binding and the launchers (``cand_cases.arm`` mirrors them and is asserted for every case):
 
-    test_index_scan            index_scan_kernel<SHUF, MT, NW>, both layouts: M 1 / 16 -> MT 1, 17 / 32 -> MT 2 (NW 4),
+    test_index_scan            index_scan_kernel<FMT, MT, NW, 8>, both layouts: M 1 / 16 -> MT 1, 17 / 32 -> MT 2 (NW 4),
                                33 .. 96 -> MT 3 .. 6 (NW 8), a ragged last query tile at 17, 33, 49, 65, 81;
                                K 256, 768 (M 96), 1024 (M 64); N 4, 132 and P + 132 with P = 256 x CUs rows of one
                                grid pass: the VGPR ring crosses a tile boundary and some workgroups run a partial

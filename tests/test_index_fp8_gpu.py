@@ -1,5 +1,5 @@
-"""The opt-in FP8 vector index on the GPU: ``index_scan_fp8_kernel`` (the FP8 arm of the persistent index scan),
-``index_dequant_kernel`` and ``VectorIndex`` with ``dtype=torch.float8_e4m3fn``.
+"""The opt-in FP8 vector index on the GPU: ``index_scan_kernel<kScanFp8, MT, NW, NWIN>`` (the FP8 arm of the persistent
+index scan), ``index_dequant_kernel`` and ``VectorIndex`` with ``dtype=torch.float8_e4m3fn``.
 
     test_fp8_scan_exact         every instantiation <MT 1-6, NW 4 / 8> on the exact operands of tests/index_fp8_cases.py
                                 (integer scores, three exponent bytes): M over cand_cases.SCAN_MK at K 256 (ring of 4

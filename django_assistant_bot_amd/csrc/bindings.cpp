@@ -230,6 +230,25 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("ldb"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
      py::arg("residual"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epilogue"), py::arg("s"),
      py::arg("b_shuf") = 0, py::arg("b_group") = 1, py::arg("rows") = 0, py::arg("src_rows") = 0);
+  m.def("gemm256_fp8", [](u A, long lda, u B, u exps, u C, long ldc, u bias, u residual, long ldr, int M, int N, int K,
+                          int epilogue, u s, int b_shuf, int b_group, u rows, int src_rows) {
+    check(dab::gemm256_fp8(CVP(A), lda, CVP(B), CVP(exps), VP(C), ldc, CVP(bias), CVP(residual), ldr, M, N, K, epilogue,
+                           ST(s), b_shuf, b_group, reinterpret_cast<const int*>(rows), src_rows),
+          "gemm256_fp8");
+  }, py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("exps"), py::arg("C"), py::arg("ldc"), py::arg("bias"),
+     py::arg("residual"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epilogue"), py::arg("s"),
+     py::arg("b_shuf") = 1, py::arg("b_group") = 1, py::arg("rows") = 0, py::arg("src_rows") = 0);
+  m.def("gemm256_candidates_fp8", [](u A, long lda, u W8, u exps, long exps_n, int M, int N, int K, u row_group,
+                                     u q_group, u thr, u cnt, u cand_val, u cand_idx, int cap, u s, int b_rows) {
+    check(dab::gemm256_candidates_fp8(CVP(A), lda, CVP(W8), CVP(exps), exps_n, M, N, K,
+                                      reinterpret_cast<const int*>(row_group), reinterpret_cast<const int*>(q_group),
+                                      reinterpret_cast<const float*>(thr), reinterpret_cast<int*>(cnt),
+                                      reinterpret_cast<float*>(cand_val), reinterpret_cast<int*>(cand_idx), cap, ST(s),
+                                      b_rows),
+          "gemm256_candidates_fp8");
+  }, py::arg("A"), py::arg("lda"), py::arg("W8"), py::arg("exps"), py::arg("exps_n"), py::arg("M"), py::arg("N"),
+     py::arg("K"), py::arg("row_group"), py::arg("q_group"), py::arg("thr"), py::arg("cnt"), py::arg("cand_val"),
+     py::arg("cand_idx"), py::arg("cap"), py::arg("s"), py::arg("b_rows"));
   m.def("gemm_score_candidates", [](u A, long lda, u B, long ldb, int M, int N, int K, u row_group, u q_group, u thr,
                                     u cnt, u cand_val, u cand_idx, int cap, u s) {
     check(dab::gemm_score_candidates(CVP(A), lda, CVP(B), ldb, M, N, K, reinterpret_cast<const int*>(row_group),

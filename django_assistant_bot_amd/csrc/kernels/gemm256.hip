@@ -35,6 +35,12 @@
 //     the one copy the decode GEMM (stream_gemm.hip) streams too.  A 16-row x 32-k block is one
 //     contiguous 1 KB piece in MFMA A-fragment lane order, so each wave's LDS-DMA instruction copies
 //     a whole block and the fragment read is lane-linear (ds_read_b128 at lane * 16, no swizzle).
+//   * W8 (with SHUF): FP8 weights, e4m3fn bytes in the ops.shuffle_weights_fp8 layout
+//     [N/16][K/64][64 lanes][16 B] with one E8M0 exponent byte per row.  A 16-row x 64-k block is
+//     1 KB, so a B piece is ONE LDS-DMA instruction per wave (8 KB per half and K-tile; the counted
+//     waits become vmcnt(6)), one ds_read_b128 returns both k-steps of a fragment, fp8x8_bf16 makes
+//     them bf16 (exact), and the epilogue multiplies the fp32 accumulators by the column's power of
+//     two: bit for bit the bf16 kernel's result on the dequantised weights.
 #include "common.h"
 #include "launchers.h"
 
@@ -76,6 +82,11 @@ struct G256 {
   // [M, N]; A and the residual have src_rows rows.  Any order, duplicates allowed.
   const int* rows;
   int src_rows;
+  // W8 (FP8 weights, read by the W8 instantiations only): B is e4m3fn bytes in the
+  // ops.shuffle_weights_fp8 layout and exps holds one E8M0 exponent byte per B row; exps_n bytes of
+  // it may be read (a multiple of 4, >= 32)
+  const unsigned char* exps;
+  int exps_n;
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -139,12 +150,18 @@ __device__ __forceinline__ void tile_of(int sid, int tiles_m, int tiles_n, int G
   n0 = (inner / gsz) << 8;
 }
 
-template <int EPI, bool BIAS, bool RES, bool SHUF = false, bool STAMP = false, int SAUX = 0, bool ROWS = false>
+template <int EPI, bool BIAS, bool RES, bool SHUF = false, bool STAMP = false, int SAUX = 0, bool ROWS = false,
+          bool W8 = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
+  static_assert(!W8 || (SHUF && !BIAS && (EPI == G_NONE || EPI == G_SWIGLU8 || EPI == G_CAND)),
+                "FP8 weights: fragment layout; plain / residual / SwiGLU8 / candidate epilogues");
   __shared__ __attribute__((aligned(16))) char smem[2 * kBuf + (EPI == G_CAND ? kCandExtra : 0)];
   // stores per wave in the epilogue (the next tile's first waits count past them; the candidate
   // epilogue issues none, or drains the queue itself)
   constexpr int kEpi = EPI == G_CAND ? 0 : kEpiStores;
+  // DMA instructions every counted wait of the K-loop leaves in flight: 4 pieces of two
+  // instructions, or (W8) an A1 piece and an A0 B0 B1 triple of 2 + 2 + 1 + 1 (tables above the K-loop)
+  constexpr int kW = W8 ? 6 : 8;
 
   // Persistent: one workgroup per CU walks a strided list of tiles.  Blocks b and b+8 share an XCD,
   // so the tile ids are split into 8 contiguous chunks (bijective for any count) and the nper
@@ -242,7 +259,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   }
   // SHUF: wave w copies 16-row block w of each 128-row half, both 32-k blocks of the K-tile
   // (1 KB each, lane-linear); block (rb, kb) of a K-tile sits at byte (K / 32 rb + kb) 1 KB
-  const unsigned kblk = (unsigned)(p.K / 32) * 1024u;
+  // W8: one 64-k block per K-tile and row block (1 KB: 16 rows x 64 e4m3fn bytes), so the block
+  // stride of a row block is K / 64 KB and every B stride below is half the bf16 one
+  const unsigned kblk = (unsigned)(p.K / (W8 ? 64 : 32)) * 1024u;
   // SHUF grouped copy (p.bgrp = 8, shuffle_weights(w, 8)): the 8 blocks of a 128-row half are
   // adjacent per k chunk -- block w of the half w KB in, a k chunk 8 KB on
   const bool bgrp = SHUF && p.bgrp == 8;
@@ -260,6 +279,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   auto rsrc_b = [&](int nn) {
     // SHUF (G_CAND over an index copy): rows past the copy read zeros; they are masked as n >= N
     const long rows = SHUF ? min(256, p.rows_b - nn) : min(256, p.N - nn);
+    if (W8)  // one byte per weight
+      return make_rsrc(reinterpret_cast<const char*>(p.B) + (size_t)nn * p.K, (unsigned)(rows > 0 ? rows * p.K : 0));
     if (SHUF) return make_rsrc(p.B + (size_t)nn * p.K, (unsigned)(rows > 0 ? rows * p.K * 2 : 0));
     return make_rsrc(p.B + (size_t)nn * p.ldb, (unsigned)(((rows - 1) * p.ldb + p.K) * 2));
   };
@@ -268,6 +289,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   // slot: 0 = A rows 0-127, 1 = A rows 128-255, 2 = B rows 0-127, 3 = B rows 128-255
   auto stage = [&](int buf, int slot, int kt, __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb) {
     const bool shb = SHUF && slot >= 2;  // (slot is a compile-time constant at every call)
+    if (W8 && shb) {
+      // block w of the half, the K-tile's one 64-k block: ONE instruction per piece, into the first
+      // 8 KB of the slot's region (block b at b KB; the other 8 KB stay unused)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(smem + buf * kBuf + slot * kHalf + w * 1024), 16,
+                                               slot == 2 ? vB0 : vB2, (unsigned)kt * cb, 0, 0);
+      return;
+    }
     char* dst = smem + buf * kBuf + slot * kHalf + w * (shb ? 2048 : 1024);
     const unsigned so = (unsigned)kt * (shb ? 2u * cb : 128u);
     const __amdgpu_buffer_rsrc_t r = slot < 2 ? ra : rb;
@@ -281,11 +309,22 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   const int swr = li >> 1;
   const int rdA0 = (64 * wr + li) * 128 + 16 * (g ^ swr), rdA1 = (64 * wr + li) * 128 + 16 * ((4 + g) ^ swr);
   // SHUF: block (2 wc + j) of the half at 2 KB strides (the j * 2048 below), k-step ks at + 1 KB
-  const int rdB0 = SHUF ? wc * 4096 + lane * 16 : (32 * wc + li) * 128 + 16 * (g ^ swr);
+  // W8: block (2 wc + j) at 1 KB strides; one read returns both k-steps (bytes 0-7 / 8-15)
+  const int rdB0 = W8 ? wc * 2048 + lane * 16 : SHUF ? wc * 4096 + lane * 16 : (32 * wc + li) * 128 + 16 * (g ^ swr);
   const int rdB1 = SHUF ? rdB0 + 1024 : (32 * wc + li) * 128 + 16 * ((4 + g) ^ swr);
 
   bf16x8 af[4][2];
   bf16x8 bfr[2][2][2];  // [jh][jn][ks]
+  // W8 with ROWS: the row-subset form has no register left for the converted fragments next to its
+  // row offsets, so the B fragments stay e4m3fn bytes (16 VGPRs, not 32) and are converted where the
+  // MFMAs read them, once per phase.  Its launches are a few tiles; the other W8 forms convert once,
+  // at the read.
+  constexpr bool kRawB = W8 && ROWS;
+  u32x4 braw[2][2];  // [jh][jn]
+  auto bfrag = [&](int jh, int j, int ks) {
+    if constexpr (kRawB) return fp8x8_bf16(braw[jh][j][2 * ks], braw[jh][j][2 * ks + 1]);
+    else return bfr[jh][j][ks];
+  };
   f32x4 acc[2][2][4][2];
   auto zero_acc = [&]() {
 #pragma unroll
@@ -307,20 +346,31 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   }
 #define G256_READ_B(BUF, JH)                                                                     \
   _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                \
-    const char* base = smem + (BUF) * kBuf + 2 * kHalf + (JH) * kHalf + j * 2048;                \
-    bfr[JH][j][0] = *reinterpret_cast<const bf16x8*>(base + rdB0);                               \
-    bfr[JH][j][1] = *reinterpret_cast<const bf16x8*>(base + rdB1);                               \
+    if constexpr (W8) {                                                                          \
+      const char* base = smem + (BUF) * kBuf + 2 * kHalf + (JH) * kHalf + j * 1024;              \
+      const u32x4 d = *reinterpret_cast<const u32x4*>(base + rdB0);                              \
+      if constexpr (kRawB) {                                                                     \
+        braw[JH][j] = d;                                                                         \
+      } else {                                                                                   \
+        bfr[JH][j][0] = fp8x8_bf16(d[0], d[1]);                                                  \
+        bfr[JH][j][1] = fp8x8_bf16(d[2], d[3]);                                                  \
+      }                                                                                          \
+    } else {                                                                                     \
+      const char* base = smem + (BUF) * kBuf + 2 * kHalf + (JH) * kHalf + j * 2048;              \
+      bfr[JH][j][0] = *reinterpret_cast<const bf16x8*>(base + rdB0);                             \
+      bfr[JH][j][1] = *reinterpret_cast<const bf16x8*>(base + rdB1);                             \
+    }                                                                                            \
   }
 #define G256_MFMA2(IH, JH1, JH2)                                                                 \
   __builtin_amdgcn_s_setprio(1);                                                                 \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                               \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                  \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                  \
-    acc[IH][JH1][i][j] = mfma16(bfr[JH1][j][ks], af[i][ks], acc[IH][JH1][i][j]);                 \
+    acc[IH][JH1][i][j] = mfma16(bfrag(JH1, j, ks), af[i][ks], acc[IH][JH1][i][j]);                 \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                               \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                  \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                  \
-    acc[IH][JH2][i][j] = mfma16(bfr[JH2][j][ks], af[i][ks], acc[IH][JH2][i][j]);                 \
+    acc[IH][JH2][i][j] = mfma16(bfrag(JH2, j, ks), af[i][ks], acc[IH][JH2][i][j]);                 \
   __builtin_amdgcn_s_setprio(0);
 
   const int T = p.K >> 6;  // K-tiles (even, >= 2)
@@ -334,7 +384,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   stage(1, 0, 1, rA, rB);
   stage(1, 2, 1, rA, rB);
   stage(1, 3, 1, rA, rB);
-  wait_vm<8>();
+  wait_vm<kW>();
   bar();
 
   // One iteration = 4 phases = K-tiles e = 2it (buffer 0) and o = 2it + 1 (buffer 1); a phase is
@@ -353,6 +403,30 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
   // the 8-phase form (one quadrant per phase), same registers (the B fragments of both halves
   // stay live across a phase pair as before).  One copy of the body: the variants differ only in
   // uniform (SGPR) values, which keeps hipcc's register allocation of the loop intact.
+  //
+  // W8: an A piece is still two instructions, a B piece is ONE.  The VM queue retires in issue order,
+  // so a wait must leave exactly the instructions issued after the pieces the next phase reads.
+  // Issue order per iteration: A1 o | A0 B0 B1 e+2 | A1 e+2 | A0 B0 B1 o+2  (2 | 2 1 1 | 2 | 2 1 1).
+  // phase : queue before the wait, oldest first (instructions)               needs        may stay
+  //   pro : A0 B0 B1 e (4)  A1 e (2)  A0 B0 B1 o (4)                          A0 B0 B1 e   2 + 4 = 6
+  //   1   : A1 e (2)  A0 B0 B1 o (4)  A1 o (2)                                A1 e         4 + 2 = 6
+  //   2   : A0 B0 B1 o (4)  A1 o (2)  A0 B0 B1 e+2 (4)                        A0 B0 B1 o   2 + 4 = 6
+  //   3   : A1 o (2)  A0 B0 B1 e+2 (4)  A1 e+2 (2)                            A1 o         4 + 2 = 6
+  //   4   : A0 B0 B1 e+2 (4)  A1 e+2 (2)  A0 B0 B1 o+2 (4)                    A0 B0 B1 e+2 2 + 4 = 6
+  // What stays in flight is always one A1 piece and one A0 B0 B1 triple (2 + 2 + 1 + 1), whichever came
+  // first, so the count is 6 in every phase (the bf16 table is the same with every piece at 2: 8).
+  // fe (first iteration after an epilogue): the kEpi stores were issued after the next tile's
+  //   A0 B0 B1 0, A1 0, A0 B0 B1 1 and before this iteration's A1 o:
+  //   1   : A1 e (2)  A0 B0 B1 o (4)  stores (kEpi)  A1 o (2)                 A1 e         6 + kEpi
+  //   2   : A0 B0 B1 o (4)  stores (kEpi)  A1 o (2)  A0 B0 B1 e+2 (4)         A0 B0 B1 o   6 + kEpi
+  //   3   : stores (kEpi)  A1 o (2)  A0 B0 B1 e+2 (4)  A1 e+2 (2)             A1 o         6 (the stores
+  //         are older than A1 o, so they are retired with it: the plain count)
+  // Drain (last iteration of the last tile): phase 1 stages A1 o as always (count 6); phases 2-4 stage
+  // nothing, and phase 2 waits vmcnt(0), which covers A0 B0 B1 o and A1 o for phases 3 and 4.
+  // K = 128 (one iteration) is the prologue followed by that last iteration: the prologue leaves
+  // A1 e, A0 B0 B1 o in flight, which is the phase-1 row above.
+  // The exponent bytes of the epilogue are scalar loads (lgkmcnt): the VM queue never sees them.
+  // (kW, above, is that count.)
   bool after_epi = false;
   int tile_no = 0;
   unsigned long long st_t0 = 0, st_t1 = 0;
@@ -397,8 +471,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
           asm volatile("" : "+v"(vA0), "+v"(vA1), "+v"(vA2), "+v"(vA3));
         }
       }
-      if (fe) wait_vm<8 + kEpi>();
-      else wait_vm<8>();
+      if (fe) wait_vm<kW + kEpi>();
+      else wait_vm<kW>();
       read_bar();
       G256_MFMA2(0, 0, 1)
       bar();
@@ -408,8 +482,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
         stage(0, 0, ke, sa, sb);
         stage(0, 2, ke, sa, sb);
         stage(0, 3, ke, sa, sb);
-        if (fe) wait_vm<8 + kEpi>();
-        else wait_vm<8>();
+        if (fe) wait_vm<kW + kEpi>();
+        else wait_vm<kW>();
       } else {
         wait_vm<0>();
       }
@@ -424,7 +498,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
       G256_READ_B(1, 1)
       if (st) {
         stage(0, 1, ke, sa, sb);
-        wait_vm<8>();
+        wait_vm<kW>();
       }
       read_bar();
       G256_MFMA2(0, 0, 1)
@@ -435,7 +509,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
         stage(1, 0, ko, sa, sb);
         stage(1, 2, ko, sa, sb);
         stage(1, 3, ko, sa, sb);
-        wait_vm<8>();
+        wait_vm<kW>();
       }
       read_bar();
       if (h2) {
@@ -453,7 +527,44 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
     // The lane offsets go through an opaque asm so hipcc cannot hoist the epilogue's address
     // arithmetic out of the tile loop (it would stay live across the K-loop and spill).
     int e_li = li, e_g = g, e_wc = wc;
+    if constexpr (W8) {
+      // the lane id is read again here (two v_mbcnt), so li and g need not stay live across the
+      // K-loop, whose fragment conversions leave no spare register
+      int e_lane;
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(e_lane));
+      e_li = e_lane & 15, e_g = e_lane >> 4;
+    }
     asm volatile("" : "+v"(e_li), "+v"(e_g), "+v"(e_wc));
+    // W8: sc[jh][jn][r] = 2^(exponent byte - 127) of this lane's column
+    // n0 + 128 jh + 32 wc + 16 jn + 4 g + r; every accumulator is read through acc_at, i.e. scaled
+    // before any epilogue step.  The 32 bytes of a (jh, wc) are wave-uniform: scalar loads from the
+    // constant address space (they count on lgkmcnt, so the VM queue and the counted waits of the next
+    // tile's prefetch do not see them), and lane group g picks dword 4 jn + g.  A candidate launch's
+    // last tile can reach past the copy (tiles_n = ceil(N / 256), exps_n >= round_up(N, 128)): the
+    // address is clamped to the last 32 bytes, and those columns are n >= N, which the epilogue masks.
+    float sc[2][2][4];
+    if constexpr (W8) {
+      typedef const __attribute__((address_space(4))) unsigned int cu32;
+#pragma unroll
+      for (int jh = 0; jh < 2; ++jh) {
+        const int nb = min(n0 + 128 * jh + 32 * wc, p.exps_n - 32);
+        cu32* ep = (cu32*)(p.exps + nb);
+#pragma unroll
+        for (int jn = 0; jn < 2; ++jn) {
+          unsigned d0 = ep[4 * jn], d1 = ep[4 * jn + 1], d2 = ep[4 * jn + 2], d3 = ep[4 * jn + 3];
+          // (opaque: the four loads stay unconditional and the pick stays three selects; hipcc
+          // otherwise sinks each load into a divergent branch on g)
+          asm volatile("" : "+s"(d0), "+s"(d1), "+s"(d2), "+s"(d3));
+          const unsigned d = e_g == 0 ? d0 : e_g == 1 ? d1 : e_g == 2 ? d2 : d3;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) sc[jh][jn][r] = exp_scale((d >> (8 * r)) & 0xffu);
+        }
+      }
+    }
+    auto acc_at = [&](int ih, int jh, int i, int jn, int r) {
+      if constexpr (W8) return acc[ih][jh][i][jn][r] * sc[jh][jn][r];
+      else return acc[ih][jh][i][jn][r];
+    };
     const long c_rows = min(256, p.M - m0);
     const __amdgpu_buffer_rsrc_t rC = make_rsrc(p.C + (size_t)m0 * p.ldc, (unsigned)(c_rows * p.ldc * 2));
     if constexpr (EPI == G_CAND) {
@@ -486,7 +597,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                   const int b = 64 * ih + 16 * i + 8 * jh + 4 * jn + r;
-                  hb[b >> 5] |= acc[ih][jh][i][jn][r] >= t ? 1u << (b & 31) : 0u;
+                  hb[b >> 5] |= acc_at(ih, jh, i, jn, r) >= t ? 1u << (b & 31) : 0u;
                 }
           }
         for (;;) {
@@ -514,7 +625,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
               for (int L = 0; L < 3; ++L)
 #pragma unroll
                 for (int u = 0; u < (4 >> L); ++u) x[u] = (b >> (4 + L)) & 1 ? x[2 * u + 1] : x[2 * u];
-              col[q] = x[0];
+              // (W8: the picked accumulator times its column's scale, the product pass 1 compared)
+              if constexpr (W8) col[q] = x[0] * sc[jh][jn][r];
+              else col[q] = x[0];
             }
 #pragma unroll
             for (int L = 0; L < 4; ++L)
@@ -560,8 +673,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
               float o[8];
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[ih][jh][i][0][r]),
-                                                           __float_as_uint(acc[ih][jh][i][1][r]), false, false);
+                auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc_at(ih, jh, i, 0, r)),
+                                                           __float_as_uint(acc_at(ih, jh, i, 1, r)), false, false);
                 o[r] = __uint_as_float(sw[0]);
                 o[4 + r] = __uint_as_float(sw[1]);
               }
@@ -611,7 +724,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
             float o[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              float gt = acc[ih][jh][i][0][r], up = acc[ih][jh][i][1][r];
+              float gt = acc_at(ih, jh, i, 0, r), up = acc_at(ih, jh, i, 1, r);
               if constexpr (EPI == G_SWIGLU8) {
                 const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(gt), __float_as_uint(up), false, false);
                 gt = __uint_as_float(sw[0]);
@@ -690,8 +803,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(G256 p) {
             float o[8];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[ih][jh][i][0][r]),
-                                                         __float_as_uint(acc[ih][jh][i][1][r]), false, false);
+              auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc_at(ih, jh, i, 0, r)),
+                                                         __float_as_uint(acc_at(ih, jh, i, 1, r)), false, false);
               o[r] = __uint_as_float(sw[0]);
               o[4 + r] = __uint_as_float(sw[1]);
             }
@@ -786,6 +899,43 @@ int gemm256_candidates(const void* A, long lda, const void* B, long ldb, int M, 
   const int nwg = tiles > cus ? cus : (int)tiles;
   if (b_rows > 0) hipLaunchKernelGGL((gemm256_kernel<G_CAND, false, false, true>), dim3(nwg), dim3(512), 0, s, p);
   else hipLaunchKernelGGL((gemm256_kernel<G_CAND, false, false>), dim3(nwg), dim3(512), 0, s, p);
+  return hipGetLastError();
+}
+
+// The same over FP8 rows: B = e4m3fn bytes in the shuffle_weights_fp8 layout (b_rows >= N rows,
+// b_rows % 16 == 0), exps = one E8M0 byte per row, of which exps_n >= max(N, 32) may be read (4-byte
+// aligned).  Candidate sets and values equal gemm256_candidates on the dequantised rows.
+int gemm256_candidates_fp8(const void* A, long lda, const void* B, const void* exps, long exps_n, int M, int N, int K,
+                           const int* row_group, const int* q_group, const float* thr, int* cnt, float* cand_val,
+                           int* cand_idx, int cap, hipStream_t s, int b_rows) {
+  if (M <= 0 || N <= 0) return 0;
+  if (K % 128 || K <= 0 || lda % 8 || cap <= 0 || !B || !exps) return hipErrorInvalidValue;
+  if ((255L * lda + K) * 2 >= (1L << 31) || 256L * K >= (1L << 31)) return hipErrorInvalidValue;
+  if (b_rows < N || b_rows % 16 || exps_n < N || exps_n < 32 || ((uintptr_t)exps & 3)) return hipErrorInvalidValue;
+  G256 p{};
+  p.A = (const bf16*)A;
+  p.B = (const bf16*)B;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.lda = lda;
+  p.ldb = K;
+  p.gm = 4;
+  p.row_group = row_group;
+  p.q_group = q_group;
+  p.thr = thr;
+  p.cnt = cnt;
+  p.cand_val = cand_val;
+  p.cand_idx = cand_idx;
+  p.cap = cap;
+  p.rows_b = b_rows;
+  p.exps = (const unsigned char*)exps;
+  p.exps_n = (int)((exps_n > (1L << 30) ? (1L << 30) : exps_n) & ~3L);
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
+  const int nwg = tiles > cus ? cus : (int)tiles;
+  hipLaunchKernelGGL((gemm256_kernel<G_CAND, false, false, true, false, 0, false, true>), dim3(nwg), dim3(512), 0, s, p);
   return hipGetLastError();
 }
 
@@ -977,6 +1127,62 @@ int gemm256(const void* A, long lda, const void* B, long ldb, void* C, long ldc,
   }
 #undef G256_LAUNCH
 #undef G256_LAUNCH_AUX
+  return hipGetLastError();
+}
+
+// FP8 weights (W8A16): B = e4m3fn bytes in the ops.shuffle_weights_fp8(data, b_group) layout [N, K],
+// exps = one E8M0 exponent byte per weight row [N] (4-byte aligned).  Bit for bit what gemm256 gives
+// with b_shuf on shuffle_weights(weight_dequantize_fp8(data, exps), b_group).  Epilogues 0 (+ residual)
+// and 4, with or without rows; a bias, GELU, the 16-row SwiGLU and the row-major layout (b_shuf == 0)
+// are refused before any launch.
+int gemm256_fp8(const void* A, long lda, const void* B, const void* exps, void* C, long ldc, const void* bias,
+                const void* residual, long ldr, int M, int N, int K, int epilogue, hipStream_t s, int b_shuf,
+                int b_group, const int* rows, int src_rows) {
+  if (!b_shuf || bias || !B || !exps || ((uintptr_t)exps & 3)) return hipErrorInvalidValue;
+  if (epilogue != G_NONE && epilogue != G_SWIGLU8) return hipErrorInvalidValue;
+  if (epilogue == G_SWIGLU8 && residual) return hipErrorInvalidValue;
+  if (b_group != 1 && b_group != 8) return hipErrorInvalidValue;
+  if (!gemm256_ok(M, N, K, lda, K)) return hipErrorInvalidValue;
+  if (rows) {
+    if (src_rows <= 0) return hipErrorInvalidValue;
+    if (((long)(src_rows - 1) * lda + K) * 2 >= (1L << 31)) return hipErrorInvalidValue;
+    if (residual && ((long)(src_rows - 1) * ldr + N) * 2 >= (1L << 31)) return hipErrorInvalidValue;
+  }
+  G256 p{};
+  p.A = (const bf16*)A;
+  p.B = (const bf16*)B;
+  p.C = (bf16*)C;
+  p.residual = (const bf16*)residual;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.lda = lda;
+  p.ldb = K;
+  p.ldc = ldc;
+  p.ldr = ldr;
+  p.rows_b = N;
+  p.bgrp = b_group;
+  p.rows = rows;
+  p.src_rows = src_rows;
+  p.exps = (const unsigned char*)exps;
+  p.exps_n = N;
+  p.gm = 4;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int tiles = ((M + 255) / 256) * (N / 256);
+  const int nwg = tiles > cus ? cus : tiles;
+#define G256_LAUNCH_W8(E, R, RW) \
+  hipLaunchKernelGGL((gemm256_kernel<E, false, R, true, false, 0, RW, true>), dim3(nwg), dim3(512), 0, s, p)
+  if (rows) {
+    if (epilogue == G_SWIGLU8) G256_LAUNCH_W8(G_SWIGLU8, false, true);
+    else if (residual) G256_LAUNCH_W8(G_NONE, true, true);
+    else G256_LAUNCH_W8(G_NONE, false, true);
+  } else {
+    if (epilogue == G_SWIGLU8) G256_LAUNCH_W8(G_SWIGLU8, false, false);
+    else if (residual) G256_LAUNCH_W8(G_NONE, true, false);
+    else G256_LAUNCH_W8(G_NONE, false, false);
+  }
+#undef G256_LAUNCH_W8
   return hipGetLastError();
 }
 

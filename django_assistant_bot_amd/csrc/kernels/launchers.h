@@ -95,6 +95,18 @@ int gemm256_stamped(const void* A, long lda, const void* B, void* C, const void*
 int gemm256(const void* A, long lda, const void* B, long ldb, void* C, long ldc, const void* bias,
             const void* residual, long ldr, int M, int N, int K, int epilogue, hipStream_t s, int b_shuf = 0,
             int b_group = 1, const int* rows = nullptr, int src_rows = 0);
+// ... with FP8 weights (W8A16): B = e4m3fn bytes in the ops.shuffle_weights_fp8(data, b_group) layout,
+// exps = one E8M0 exponent byte per weight row [N] (4-byte aligned).  The same numbers as gemm256 with
+// b_shuf on the dequantised weights.  Epilogues 0 (+ residual) and 4, rows optional; a bias, any other
+// epilogue or b_shuf == 0 -> hipErrorInvalidValue (nothing is launched)
+int gemm256_fp8(const void* A, long lda, const void* B, const void* exps, void* C, long ldc, const void* bias,
+                const void* residual, long ldr, int M, int N, int K, int epilogue, hipStream_t s, int b_shuf = 1,
+                int b_group = 1, const int* rows = nullptr, int src_rows = 0);
+// ... and the candidate search over FP8 index rows (b_rows >= N rows of bytes, b_rows % 16 == 0; exps_n >=
+// max(N, 32) exponent bytes readable): one launch for any M, K % 128 == 0
+int gemm256_candidates_fp8(const void* A, long lda, const void* B, const void* exps, long exps_n, int M, int N, int K,
+                           const int* row_group, const int* q_group, const float* thr, int* cnt, float* cand_val,
+                           int* cand_idx, int cap, hipStream_t s, int b_rows);
 
 // gemm_mid.hip (M = 256..4096: mixed serving steps / single prompts; grouped stream-K over the N x K
 // plane, 128 x 256 tiles, in-launch last-arriver combine; B in the shuffle_weights layout;

@@ -96,6 +96,14 @@ def _bucket_sizes(max_batch):
     return [x for x in b if x < max_batch] + [max_batch]
 
 
+def parse_flag(v) -> bool:
+    """An on / off setting or environment value: 1 / true / yes / on (any case) are on, anything else,
+    the empty string and None are off."""
+    if isinstance(v, str):
+        return v.strip().lower() in ("1", "true", "yes", "on")
+    return bool(v)
+
+
 class LLMEngine:
     def __init__(self, model: str | DecoderConfig = "llama-3-8b", device=None, weights: dict | None = None,
                  checkpoint: str | None = None, seed: int = 0, max_batch: int = 256, block_size: int = 64,
@@ -105,7 +113,7 @@ class LLMEngine:
                  part_size: int = 512, kv_memory_fraction: float = 0.85, mixed_prefill_tokens: int = 0,
                  pipeline_decode: bool = True, shared_model: LlamaModel | None = None,
                  kv_cache_dtype: str | None = None, kv_scratch_blocks: int | None = None,
-                 weight_dtype: str | None = None):
+                 weight_dtype: str | None = None, fp8_weights_only: bool | None = None):
         """``shared_model``: serve with another engine's ``LlamaModel`` (one copy of the weights, a
         KV pool / scheduler / HIP graphs of this engine's own; e.g. two engines on two streams whose
         prefill and decode phases overlap: bench.py --mode overlap).
@@ -118,7 +126,14 @@ class LLMEngine:
         ``weight_dtype``: ``"bf16"`` or ``"fp8"`` (opt-in FP8 projection weights for the streaming
         decode GEMM, ``LlamaModel(weight_dtype=...)``: docs/ARCHITECTURE.md "FP8 weights"); ``None``
         reads ``DAB_WEIGHT_DTYPE`` from the environment, else bf16.  With ``shared_model`` the engine
-        adopts the model's; a conflicting argument raises."""
+        adopts the model's; a conflicting argument raises.
+
+        ``fp8_weights_only`` (opt-in on top of ``weight_dtype="fp8"``, TP 1): the FP8 bytes are the only
+        copy of every projection (``LlamaModel(fp8_weights_only=True)``: a capacity feature, the freed
+        memory goes to KV blocks); ``None`` reads ``DAB_WEIGHT_FP8_ONLY`` (1 / true / yes / on) from the
+        environment, else off.  Refused (ValueError) without ``weight_dtype="fp8"``, under TP and on
+        the GPU for projections gemm256 does not take; with ``shared_model`` the engine adopts the
+        model's."""
         self.cfg = decoder_config(model) if isinstance(model, str) else model
         cfg = self.cfg
         if shared_model is not None:
@@ -126,13 +141,25 @@ class LLMEngine:
             if weight_dtype is not None and weight_dtype != have:
                 raise ValueError(f"weight_dtype={weight_dtype!r} conflicts with the shared model's {have!r}")
             weight_dtype = have
+            have_only = bool(getattr(shared_model, "fp8_weights_only", False))
+            if fp8_weights_only is not None and bool(fp8_weights_only) != have_only:
+                raise ValueError(f"fp8_weights_only={fp8_weights_only!r} conflicts with the shared model's {have_only!r}")
+            fp8_weights_only = have_only
         elif weight_dtype is None:
             weight_dtype = os.environ.get("DAB_WEIGHT_DTYPE") or "bf16"
+        if fp8_weights_only is None:
+            fp8_weights_only = parse_flag(os.environ.get("DAB_WEIGHT_FP8_ONLY"))
+        fp8_weights_only = bool(fp8_weights_only)
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
         if weight_dtype == "fp8" and tp_size > 1:
             raise ValueError("weight_dtype='fp8' does not support tensor parallelism (tp_size > 1) yet")
+        if fp8_weights_only and weight_dtype != "fp8":
+            raise ValueError("fp8_weights_only needs weight_dtype='fp8'")
+        if fp8_weights_only and tp_size > 1:
+            raise ValueError("fp8_weights_only does not support tensor parallelism (tp_size > 1)")
         self.weight_dtype = weight_dtype
+        self.fp8_weights_only = fp8_weights_only
         if kv_cache_dtype is None:
             kv_cache_dtype = os.environ.get("DAB_KV_CACHE_DTYPE") or "bf16"
         if kv_cache_dtype not in ("bf16", "fp8"):
@@ -166,7 +193,7 @@ class LLMEngine:
         else:
             self.model = LlamaModel(cfg, weights, self.device, tp_group=tp_group, tp_size=tp_size,
                                     interleaved_mlp=interleaved_mlp, consume=own_weights, tp_rank=tp_rank,
-                                    weight_dtype=weight_dtype)
+                                    weight_dtype=weight_dtype, fp8_weights_only=fp8_weights_only)
         del weights
         if self.is_gpu and shared_model is None:
             # the caller's weight dict held the row-major originals while the model converted them
@@ -225,7 +252,11 @@ class LLMEngine:
                       # every other entry, since consumers subtract two snapshots of this dict
                       "kv_cache_bits": 8 if fp8 else 16,
                       # the projection weights the decode GEMM streams (8: ``weight_dtype="fp8"``)
-                      "weight_bits": 8 if weight_dtype == "fp8" else 16}
+                      "weight_bits": 8 if weight_dtype == "fp8" else 16,
+                      # whether the projections keep a bf16 copy (False: ``fp8_weights_only``), and the
+                      # projection bytes resident, counted from the model's tensors
+                      "weight_bf16_copy": not fp8_weights_only,
+                      "weight_bytes": self.model.projection_bytes()}
         # decode static buffers (graph inputs / outputs)
         self.use_graphs = use_graphs and self.is_gpu
         dev = self.device

@@ -432,12 +432,19 @@ class VectorIndex:
         return got
 
     CAND_BYTES = 256 << 20  # candidate-list memory of one threshold search
+    FP8_WIDE_MIN_M = 97  # FP8 index: batches from here on (and above one scan launch) take one gemm256 launch
 
     def _threshold_candidates(self, q, thr, k: int, cap: int, n4: int, qg):
-        if self.frag8:  # the FP8 scan, in groups of the queries one launch takes
+        if self.frag8:
+            # up to one scan launch of queries: the persistent FP8 scan.  More: ONE launch of gemm256's
+            # candidate epilogue on its FP8 arm from FP8_WIDE_MIN_M queries on (the rows are streamed
+            # once, profiles/gemm256_fp8.md); the scan in groups of a launch's queries below that
+            # and at widths gemm256 does not take.
             step = ops.fp8_scan_max_m(self.dim)
+            if q.shape[0] > step and q.shape[0] >= self.FP8_WIDE_MIN_M and self.dim % 128 == 0:
+                step = q.shape[0]
             parts = [ops.score_candidates_fp8(q[a:a + step], self.vecs, self.exps, n4, thr[a:a + step], cap,
-                                              self.row_group[:n4], None if qg is None else qg[a:a + step])
+                                              self.row_group[:n4], None if qg is None else qg[a:a + step], wide=True)
                      for a in range(0, q.shape[0], step)]
             cand_val, cand_idx, cnt = parts[0]
             if len(parts) > 1:

@@ -45,26 +45,34 @@ class Fp8Proj:
     output row, streamed by the decode GEMM (stream_gemm's FP8 arm), and ``w``, a bf16
     ``ops.shuffle_weights`` copy of the DEQUANTISED values for the MFMA GEMMs (gemm256 / gemm_mid /
     gemm_bt).  Both hold the same numbers, so prefill, mixed steps and every decode batch compute
-    with identical weights.  ``group``: the row-block group of both copies."""
+    with identical weights.  ``group``: the row-block group of both copies.
+
+    ``fp8_weights_only``: ``w`` is None and the FP8 bytes are the ONLY copy; the MFMA GEMMs then run
+    the FP8 arm of gemm256 (``ops.gemm_bt(..., w_exps=)``), which gives the same numbers."""
 
     __slots__ = ("w", "data", "exps", "group")
 
-    def __init__(self, w: torch.Tensor, data: torch.Tensor, exps: torch.Tensor, group: int = 1):
+    def __init__(self, w: torch.Tensor | None, data: torch.Tensor, exps: torch.Tensor, group: int = 1):
         self.w, self.data, self.exps, self.group = w, data, exps, group
 
     @classmethod
-    def from_rows(cls, data: torch.Tensor, exps: torch.Tensor, group: int = 1) -> "Fp8Proj":
+    def from_rows(cls, data: torch.Tensor, exps: torch.Tensor, group: int = 1, bf16_copy: bool = True) -> "Fp8Proj":
         """From row-major e4m3fn bytes [N, K] and row exponents [N] (``ops.weight_quantize_fp8``)."""
-        return cls(ops.shuffle_weights(ops.weight_dequantize_fp8(data, exps), group),
-                   ops.shuffle_weights_fp8(data, group), exps.contiguous(), group)
+        w = ops.shuffle_weights(ops.weight_dequantize_fp8(data, exps), group) if bf16_copy else None
+        return cls(w, ops.shuffle_weights_fp8(data, group), exps.contiguous(), group)
 
     @property
     def shape(self):
-        return self.w.shape
+        return self.data.shape  # [N, K], as the bf16 copy's
+
+    def nbytes(self) -> int:
+        """Bytes resident for this projection, counted from its tensors."""
+        return sum(t.numel() * t.element_size() for t in (self.w, self.data, self.exps) if t is not None)
 
     def regroup(self, group: int) -> None:
         """Re-lay both copies for ``group``, in place (pointers stay valid)."""
-        self.w.copy_(ops.shuffle_weights(ops.unshuffle_weights(self.w, self.group), group))
+        if self.w is not None:
+            self.w.copy_(ops.shuffle_weights(ops.unshuffle_weights(self.w, self.group), group))
         self.data.copy_(ops.shuffle_weights_fp8(ops.unshuffle_weights_fp8(self.data, self.group), group))
         self.group = group
 
@@ -201,7 +209,7 @@ class LlamaModel:
     def __init__(self, cfg: DecoderConfig, weights: dict, device, tp_group=None, tp_size: int = 1,
                  interleaved_mlp: bool = False, fragment_layout: bool = True, consume: bool = False,
                  tp_rank: int | None = None, vocab_parallel: bool = True, small_norm_fused: bool | None = None,
-                 weight_dtype: str = "bf16"):
+                 weight_dtype: str = "bf16", fp8_weights_only: bool = False):
         """``weight_dtype="fp8"`` (opt-in, TP 1): the qkv / o / gate_up / down weights are quantised at
         load time to e4m3fn bytes with one power-of-two exponent per output row
         (``ops.weight_quantize_fp8``) and the model computes with the dequantised values everywhere.
@@ -210,6 +218,15 @@ class LlamaModel:
         bf16 copy of the same values.  A bandwidth feature, not a capacity one: the projections take
         1.5x the bf16 model's memory.  Embedding, norms and LM head stay bf16.  On the CPU (or
         without the fragment layout) the weights are the dequantised row-major tensors.
+
+        ``fp8_weights_only`` (opt-in on top of ``weight_dtype="fp8"``, TP 1, fragment layout): the FP8
+        bytes are the only copy of every projection (half the bf16 model's projection memory, a third
+        of the two-copy FP8 model's).  Streamed calls read them through stream_gemm's FP8 arm, every
+        other call through the FP8 arm of gemm256 (``ops.gemm_bt(..., w_exps=)``) at any M, so
+        gemm_mid and the 128 x 128 kernel are never reached and every projection needs N % 256 == 0
+        and K % 128 == 0 on the GPU (ValueError otherwise).  The numbers are those of the two-copy model
+        wherever that one takes gemm256 or stream_gemm; elsewhere they differ in accumulation order only.
+        On the CPU it changes nothing (the model already runs on dequantised row-major weights).
 
         ``consume``: the entries of ``weights`` are popped as the model takes them over, so each
         original is freed as soon as its fragment-layout copy exists (peak HBM = model + one
@@ -226,6 +243,14 @@ class LlamaModel:
         if weight_dtype == "fp8" and tp_size > 1:
             raise ValueError("weight_dtype='fp8' is not supported under tensor parallelism (tp_size > 1)")
         self.weight_dtype = weight_dtype
+        self.fp8_weights_only = bool(fp8_weights_only)
+        if self.fp8_weights_only:
+            if weight_dtype != "fp8":
+                raise ValueError("fp8_weights_only needs weight_dtype='fp8'")
+            if not fragment_layout:
+                raise ValueError("fp8_weights_only needs the fragment layout (fragment_layout=True)")
+            if not self.fp8_stream or self.FP8_STREAM_OFF:
+                raise ValueError("fp8_weights_only keeps no bf16 copy for fp8_stream=False / FP8_STREAM_OFF to stream")
         self.cfg = cfg
         self.device = torch.device(device)
         if tp_rank is None:
@@ -252,6 +277,14 @@ class LlamaModel:
         # (``fragment_layout=False``: row-major weights on the GPU too, every projection on the
         # 128x128 / phased 256x256 GEMMs -- the comparison path of tests/test_models_gpu.py)
         self.frag = fragment_layout and self.device.type == "cuda" and self._fragment_ok(weights)
+        if self.fp8_weights_only and self.device.type == "cuda":
+            if not self.frag:
+                raise ValueError("fp8_weights_only: the weights do not take the fragment layout")
+            for n in ("qkv_w", "o_w", "gate_up_w", "down_w"):
+                N, K = weights[f"l0.{n}"].shape
+                if N % 256 or K % 128:
+                    raise ValueError(f"fp8_weights_only: {n} [{N}, {K}] needs N % 256 == 0 and K % 128 == 0 "
+                                     "(the FP8 arm of gemm256 is its only MFMA kernel)")
         take = weights.pop if consume else weights.__getitem__
 
         self.proj_group = {}
@@ -268,8 +301,16 @@ class LlamaModel:
                 g = self.PROJ_GROUPS.get(name, 1)
                 self.proj_group[name] = g if (t.shape[0] % (16 * g) == 0 and t.numel() * 2 < (1 << 31)) else 1
             if fp8:
-                return Fp8Proj.from_rows(data, exps, self.proj_group[name])
+                return Fp8Proj.from_rows(data, exps, self.proj_group[name], bf16_copy=not self.fp8_weights_only)
             return ops.shuffle_weights(t, self.proj_group[name])
+
+        def load(i, name, norm=None):
+            """Projection ``name`` of layer i, built and its bf16 source released before the next one
+            is taken (the peak during load holds one projection's source, never a layer's)."""
+            t = take(f"l{i}.{name}_w").to(self.device)
+            if norm is not None:
+                t = self._fold(t, norm)
+            return fmt(name, t)
 
         self.embed = take("embed").to(self.device)
         self.final_norm = take("final_norm").to(self.device)
@@ -295,15 +336,11 @@ class LlamaModel:
         for i in range(cfg.layers):
             an = take(f"l{i}.attn_norm").to(self.device)
             mn = take(f"l{i}.mlp_norm").to(self.device)
-            qkv_w, gu_w = take(f"l{i}.qkv_w").to(self.device), take(f"l{i}.gate_up_w").to(self.device)
-            if self.fold_norms:
-                qkv_w, an = self._fold(qkv_w, an), torch.ones_like(an)
-                gu_w, mn = self._fold(gu_w, mn), torch.ones_like(mn)
-            o_w, down_w = take(f"l{i}.o_w").to(self.device), take(f"l{i}.down_w").to(self.device)
-            self.layers.append(DecoderLayer(an, fmt("qkv", qkv_w), fmt("o", o_w), mn, fmt("gate_up", gu_w),
-                                            fmt("down", down_w)))
-            del o_w, down_w
-            del qkv_w, gu_w
+            fold = self.fold_norms
+            qkv_w, gu_w = load(i, "qkv", an if fold else None), load(i, "gate_up", mn if fold else None)
+            if fold:
+                an, mn = torch.ones_like(an), torch.ones_like(mn)
+            self.layers.append(DecoderLayer(an, qkv_w, load(i, "o"), mn, gu_w, load(i, "down")))
         if self.frag and consume:
             torch.cuda.empty_cache()
 
@@ -335,6 +372,14 @@ class LlamaModel:
         parts = [torch.empty_like(src) for _ in range(self.tp_size)]
         dist.all_gather(parts, src, group=self.tp_group)
         return torch.cat(parts, 1).to(local.device)
+
+    def projection_bytes(self) -> int:
+        """Bytes of the qkv / o / gate_up / down weights resident, every copy, counted from the tensors."""
+        total = 0
+        for L in self.layers:
+            for w in (L.qkv_w, L.o_w, L.gate_up_w, L.down_w):
+                total += w.nbytes() if isinstance(w, Fp8Proj) else w.numel() * w.element_size()
+        return total
 
     def set_proj_group(self, name: str, group: int) -> None:
         """Re-lay every layer's copy of projection ``name`` (qkv / o / gate_up / down) as
@@ -464,6 +509,8 @@ class LlamaModel:
         grp = self.proj_group.get(name, 1)
         if dec and self.frag:
             cfg, s = self._stream_choice(name, x.shape[0], w.shape[0], w.shape[1])
+            if cfg >= 0 and self.fp8_weights_only and not ops.native().stream_gemm_fp8_ok(cfg):
+                cfg = -1  # no FP8 instantiation of this tiling and no bf16 copy to stream: gemm256's FP8 arm
             if cfg >= 0:
                 sw, e = self._stream_w(w, name, cfg)
                 if epilogue != ops.EPI_NONE:
@@ -471,7 +518,14 @@ class LlamaModel:
                 sd = torch.bfloat16 if (self.slab_bf16 and self.tp_size == 1 and not slab_f32) else torch.float32
                 out = ops.stream_gemm(x, sw, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp, w_exps=e)
                 return ops.slab_reduce(out) if (s > 1 and not allow_slabs) else out
-        return ops.gemm_bt(x, _bf16_copy(w), epilogue=epilogue, shuffled=self.frag, b_group=grp)
+        return self._mfma(x, w, epilogue=epilogue, shuffled=self.frag, b_group=grp)
+
+    def _mfma(self, x, w, **kw):
+        """``ops.gemm_bt`` on a projection: its bf16 copy, or (``fp8_weights_only``: there is none) the
+        FP8 bytes on the FP8 arm of gemm256, which takes every M."""
+        if isinstance(w, Fp8Proj) and w.w is None:
+            return ops.gemm_bt(x, w.data, w_exps=w.exps, **kw)
+        return ops.gemm_bt(x, _bf16_copy(w), **kw)
 
     # FP8 weights: (projection, stream_gemm cfg) pairs that stream the bf16 copy although the cfg has
     # an FP8 instantiation: the per-shape opt-out for ranges that measure slower (profiles/weight_fp8.md)
@@ -485,6 +539,9 @@ class LlamaModel:
             return w, None
         if self.fp8_stream and ops.native().stream_gemm_fp8_ok(cfg) and (name, cfg) not in self.FP8_STREAM_OFF:
             return w.data, w.exps
+        if w.w is None:
+            raise RuntimeError(f"fp8_weights_only: stream_gemm cfg {cfg} ({name}) has no FP8 arm (or FP8 streaming "
+                               "was switched off) and there is no bf16 copy to stream")
         return w.w, None
 
     # Pure prefill steps whose caller reads only ``out_rows`` (the last token of each finished
@@ -499,7 +556,11 @@ class LlamaModel:
 
     def _tail_prunable(self, T: int, meta: AttnMeta, x: torch.Tensor, sk: bool) -> bool:
         if not (self.prune_last_tail and x.is_cuda and not sk and not meta.decode and not meta.n_decode
-                and self.tp_size == 1 and self.frag and T >= ops.kernels.GEMM256_MIN_M):
+                and self.tp_size == 1 and self.frag):
+            return False
+        if self.fp8_weights_only:
+            return True  # every call that is not streamed is gemm256 (its FP8 arm), at any T
+        if T < ops.kernels.GEMM256_MIN_M:
             return False
         L = self.layers[-1]
         for N, K in (L.o_w.shape, L.gate_up_w.shape, L.down_w.shape):  # (contiguous activations: lda = K)
@@ -669,20 +730,19 @@ class LlamaModel:
         if rows.dtype != torch.int32:
             rows = rows.to(torch.int32)
         pg = self.proj_group
-        res = ops.gemm_bt(a.view(T, self.hq * D), _bf16_copy(L.o_w), residual=residual, shuffled=True,
-                          b_group=pg.get("o", 1), rows=rows)
+        res = self._mfma(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=True,
+                         b_group=pg.get("o", 1), rows=rows)
         h, _ = ops.rmsnorm(res, L.mlp_norm, self.cfg.eps)
-        act = ops.gemm_bt(h, _bf16_copy(L.gate_up_w), epilogue=ops.EPI_SWIGLU8, shuffled=True,
-                          b_group=pg.get("gate_up", 1), as_m=T)
-        return None, ops.gemm_bt(act, _bf16_copy(L.down_w), residual=res, shuffled=True, b_group=pg.get("down", 1),
-                                 as_m=T)
+        act = self._mfma(h, L.gate_up_w, epilogue=ops.EPI_SWIGLU8, shuffled=True,
+                         b_group=pg.get("gate_up", 1), as_m=T)
+        return None, self._mfma(act, L.down_w, residual=res, shuffled=True, b_group=pg.get("down", 1), as_m=T)
 
     def _layer_tail(self, L, a, residual, sk, fuse, slabs_ok, T, D):
         """o projection, MLP norm, gate_up (+SwiGLU), down: -> (next layer input, residual stream)."""
         cfg = self.cfg
         if fuse:
-            residual = ops.gemm_bt(a.view(T, self.hq * D), _bf16_copy(L.o_w), residual=residual, shuffled=self.frag,
-                                   b_group=self.proj_group.get("o", 1))
+            residual = self._mfma(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=self.frag,
+                                  b_group=self.proj_group.get("o", 1))
             h, _ = ops.rmsnorm(residual, L.mlp_norm, cfg.eps)
         elif sk and self.tp_size > 1:
             # TP decode: the o partial (split-K slabs) meets its all-reduce inside the MLP norm's launch
@@ -697,8 +757,8 @@ class LlamaModel:
         if h.is_cuda and epi == ops.EPI_NONE:
             act = ops.silu_mul(act)
         if fuse:
-            return None, ops.gemm_bt(act, _bf16_copy(L.down_w), residual=residual, shuffled=self.frag,
-                                     b_group=self.proj_group.get("down", 1))
+            return None, self._mfma(act, L.down_w, residual=residual, shuffled=self.frag,
+                                    b_group=self.proj_group.get("down", 1))
         if sk and self.tp_size > 1:  # reduced inside the next layer's (or the final) norm launch
             return self._tp_partial(self._proj(act, L.down_w, sk, True, name="down"), cfg.hidden), residual
         x = self._all_reduce(self._proj(act, L.down_w, sk, slabs_ok, name="down"))

@@ -584,7 +584,7 @@ def use_gemm256(M: int, N: int, K: int, lda: int, ldb: int) -> bool:
 
 
 def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, row_group=None, q_group=None,
-            allow=None, out=None, shuffled=False, n=None, b_group: int = 1, rows=None, as_m=None):
+            allow=None, out=None, shuffled=False, n=None, b_group: int = 1, rows=None, as_m=None, w_exps=None):
     """C = A . B^T (+bias) (+act) (+residual) on MFMA; A [M, K], B [N, K] (K-contiguous rows).
 
     ``shuffled``: B is a ``shuffle_weights`` copy (the layout the decode GEMM streams, so a model
@@ -597,8 +597,28 @@ def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, ro
     and the residual are gathered inside the kernel; ``as_m`` makes a call on already compact rows
     take the kernel that ``as_m`` rows would.  Both hold only where that kernel is gemm256, whose
     result for an element depends neither on M nor on the row's place in a tile; any other shape
-    is refused."""
+    is refused.
+
+    ``w_exps`` (FP8 weights, W8A16): B is the uint8 ``shuffle_weights_fp8(data, b_group)`` copy of
+    the e4m3fn bytes (``shuffled=True`` required) and ``w_exps`` [N] the rows' exponent bytes.  Every
+    such call, at any M and with ``rows`` / ``as_m``, runs the FP8 arm of gemm256 (no other kernel
+    reads the bytes): plain / residual / SwiGLU8 projections with N % 256 == 0 and K % 128 == 0,
+    anything else is refused.  Bit for bit ``gemm256`` on the dequantised weights."""
     expect(b_group == 1 or (shuffled and b_group == 8), "b_group: 1, or 8 with a shuffled copy")
+    if w_exps is not None:
+        expect(shuffled, "FP8 weights (w_exps): B must be the shuffle_weights_fp8 copy (shuffled=True)")
+        expect(bias is None and epilogue in (EPI_NONE, EPI_SWIGLU8) and not out_f32 and row_group is None
+               and q_group is None and allow is None and n is None,
+               "FP8 weights (w_exps): plain / residual / SwiGLU8 projections only (the gemm256 FP8 arm)")
+        expect(rows is None or as_m is None, "row subsets: rows or as_m, not both")
+        if not A.is_cuda:
+            Bd = weight_dequantize_fp8(unshuffle_weights_fp8(B, b_group), w_exps).to(A.dtype)
+            y = ref.gemm_bt(A, Bd, None, residual, epilogue)
+            y = y if rows is None else y.index_select(0, rows.long())
+            return y if out is None else out.copy_(y)
+        if as_m is not None:
+            expect(int(as_m) >= A.shape[0], "as_m: at least the rows of A")
+        return _gemm256_fp8(A, B, w_exps, residual, epilogue, b_group, rows, out)
     if rows is not None or as_m is not None:
         expect(out_f32 is False and row_group is None and q_group is None and allow is None and bias is None
                and n is None and epilogue in (EPI_NONE, EPI_SWIGLU8),
@@ -711,11 +731,53 @@ def _gemm256_rows(A, B, residual, epilogue, shuffled, b_group, rows, as_m, out=N
     return _gemm256_into(A, B, out, None, residual, epilogue, shuffled, b_group, rows)
 
 
+def _gemm256_fp8(A, B, w_exps, residual, epilogue, b_group, rows, out, bias=None, shuffled=True):
+    """The FP8-weight arm of gemm256 (``gemm256_kernel<..., W8>``): checks, then the launch.  Every
+    refusal is raised here, before any launch."""
+    expect(A.is_cuda and A.dtype == torch.bfloat16 and A.dim() == 2 and A.stride(-1) == 1, "bf16 CUDA A [M, K] required")
+    expect(shuffled, "gemm256 FP8 arm: the row-major layout has no FP8 form (shuffled=True)")
+    expect(bias is None, "gemm256 FP8 arm: no bias")
+    expect(epilogue in (EPI_NONE, EPI_SWIGLU8), "gemm256 FP8 arm: epilogues none (+ residual) or SwiGLU8")
+    expect(b_group in (1, 8), "gemm256 FP8 arm: b_group 1 or 8")
+    expect(B.is_cuda and B.dtype == torch.uint8 and B.dim() == 2 and B.is_contiguous(),
+           "FP8 weights: B must be the contiguous uint8 shuffle_weights_fp8 copy [N, K]")
+    (M, K), N = A.shape, B.shape[0]
+    expect(B.shape[1] == K, "inner dims mismatch")
+    expect(M > 0 and bool(native().gemm256_ok(M, N, K, A.stride(0), K)), "gemm256: N % 256, K % 128, 16-B rows")
+    expect(w_exps.dtype == torch.uint8 and w_exps.is_cuda and w_exps.dim() == 1 and w_exps.shape[0] == N
+           and w_exps.is_contiguous() and w_exps.data_ptr() % 4 == 0,
+           "w_exps must be the uint8 [N] row exponents (contiguous, 4-byte aligned)")
+    same_device(A, B, w_exps, residual, rows, out)
+    n_out = N // 2 if epilogue == EPI_SWIGLU8 else N
+    expect(epilogue == EPI_NONE or residual is None, "swiglu8 epilogue takes no residual")
+    if residual is not None:
+        expect(residual.dtype == torch.bfloat16 and residual.stride(-1) == 1 and tuple(residual.shape) == (M, n_out),
+               "residual must be bf16 row-major [M, N]")
+    n = M
+    if rows is not None:
+        _i32(rows)
+        expect(rows.is_cuda and rows.dim() == 1, "rows: int32 [n] on the device")
+        n = rows.numel()
+    if out is None:
+        out = torch.empty((n, n_out), dtype=torch.bfloat16, device=A.device)
+    expect(out.dtype == torch.bfloat16 and out.stride(-1) == 1 and tuple(out.shape) == (n, n_out)
+           and (n <= 1 or out.stride(0) % 8 == 0), "bad output buffer")
+    if n == 0:
+        return out
+    native().gemm256_fp8(ptr(A), A.stride(0), ptr(B), ptr(w_exps), ptr(out), out.stride(0), 0, ptr(residual),
+                         residual.stride(0) if residual is not None else 0, n, N, K, int(epilogue), stream(A), 1,
+                         int(b_group), ptr(rows), M if rows is not None else 0)
+    return out
+
+
 def gemm256(A, B, bias=None, residual=None, epilogue=EPI_NONE, shuffled=False, b_group: int = 1, rows=None,
-            out=None):
+            out=None, w_exps=None):
     """The phased 256x256 kernel directly, for any M (``gemm_bt`` takes it from M >= 1024):
     tests and benchmarks.  N % 256 == 0, K % 128 == 0.  ``rows``: the row-subset mode (see
-    ``gemm_bt``), into ``out`` [n, N] if given."""
+    ``gemm_bt``), into ``out`` [n, N] if given.  ``w_exps``: the FP8-weight arm (see ``gemm_bt``),
+    into ``out`` if given."""
+    if w_exps is not None:
+        return _gemm256_fp8(A, B, w_exps, residual, epilogue, b_group, rows, out, bias=bias, shuffled=shuffled)
     if rows is not None:
         expect(A.is_cuda and bias is None, "gemm256 rows: CUDA operands, no bias")
         return _gemm256_rows(A, B, residual, epilogue, shuffled, b_group, rows, None, out, direct=True)
@@ -941,17 +1003,19 @@ def fp8_scan_max_m(K: int) -> int:
     return 96 if K <= 768 else 64
 
 
-def score_candidates_fp8(A, data_shuf, exps, N, thr, cap, row_group=None, q_group=None):
+def score_candidates_fp8(A, data_shuf, exps, N, thr, cap, row_group=None, q_group=None, wide: bool = False):
     """``score_candidates_shuffled`` over FP8 rows: ``data_shuf`` uint8 [R, K], e4m3fn bytes in the
     ``shuffle_weights_fp8`` layout (R >= round_up(N, 128), R % 16 == 0), ``exps`` uint8 [>= R] with one
     E8M0 exponent byte per row (``kv_quantize``).  A score is the fp32 sum over the bytes' values times
     2^(exponent byte - 127): bit-identical to ``score_candidates_shuffled`` on the dequantised rows.
-    The persistent scan of index_scan.hip only: 1..96 queries at K <= 768, 1..64 at K <= 1024,
-    K % 256 == 0 (callers split larger batches)."""
+    1..96 queries at K <= 768, 1..64 at K <= 1024 (K % 256 == 0): the persistent scan of
+    index_scan.hip.  ``wide``: a larger batch (K % 128 == 0) is ONE launch of gemm256's candidate
+    epilogue on its FP8 arm, whatever its size; without it a larger batch is refused (callers split)."""
     expect(A.is_cuda and A.dtype == torch.bfloat16, "bf16 CUDA queries required")
     M, K = A.shape
-    expect(K % 256 == 0 and K <= 1024 and 1 <= M <= fp8_scan_max_m(K),
-           "FP8 scan: K % 256 == 0, 1..96 queries at K <= 768, 1..64 at K <= 1024")
+    wide = bool(wide) and M > fp8_scan_max_m(K) and K % 128 == 0
+    expect(wide or (K % 256 == 0 and K <= 1024 and 1 <= M <= fp8_scan_max_m(K)),
+           "FP8 scan: K % 256 == 0, 1..96 queries at K <= 768, 1..64 at K <= 1024 (wide=True: more, K % 128 == 0)")
     expect(A.stride(-1) == 1 and A.stride(0) % 8 == 0, "queries must be K-contiguous with a row stride % 8 == 0")
     expect(data_shuf.is_cuda and data_shuf.dtype == torch.uint8 and data_shuf.dim() == 2 and data_shuf.is_contiguous()
            and data_shuf.shape[1] == K, "FP8 fragment copy: contiguous uint8 [R, K]")
@@ -971,6 +1035,11 @@ def score_candidates_fp8(A, data_shuf, exps, N, thr, cap, row_group=None, q_grou
     cand_val = torch.full((M, cap), float("-inf"), dtype=torch.float32, device=A.device)
     cand_idx = torch.empty((M, cap), dtype=torch.int32, device=A.device)
     cnt = torch.zeros(M, dtype=torch.int32, device=A.device)
+    if wide:
+        native().gemm256_candidates_fp8(ptr(A), A.stride(0), ptr(data_shuf), ptr(exps), exps.numel(), M, int(N), K,
+                                        ptr(row_group), ptr(q_group), ptr(thr), ptr(cnt), ptr(cand_val), ptr(cand_idx),
+                                        int(cap), stream(A), data_shuf.shape[0])
+        return cand_val, cand_idx, cnt
     native().score_candidates_fp8(ptr(A), A.stride(0), ptr(data_shuf), ptr(exps), M, int(N), K, ptr(row_group),
                                   ptr(q_group), ptr(thr), ptr(cnt), ptr(cand_val), ptr(cand_idx), int(cap), stream(A))
     return cand_val, cand_idx, cnt

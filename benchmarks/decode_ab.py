@@ -106,6 +106,12 @@ ARMS = {
     "wfp8_deep": {"_w": "fp8", "_ring": 1},
     "wkvfp8": {"_w": "fp8", "_kv": "fp8"},
     "wkvfp8_deep": {"_w": "fp8", "_kv": "fp8", "_ring": 1},
+    # the opt-in MXFP4 projection weights, likewise (weight_dtype="mxfp4": MXFP4 copies + bf16 copies of
+    # the dequantised values; "_ring" 1: the MXFP4 arm's doubled weight ring).  FP8 and MXFP4 arms in one
+    # run build one model each (the first named is the one arms without "_w" stream the bf16 copies of)
+    "wmx": {"_w": "mxfp4"},
+    "wmx_deep": {"_w": "mxfp4", "_ring": 1},
+    "wmx_off": {"_w": "mxfp4", "_stream_off": True},  # the MXFP4 model streaming its bf16 copies
 }
 
 
@@ -138,10 +144,20 @@ def main():
     from django_assistant_bot_amd.engine.llm_engine import LLMEngine, SamplingParams
 
     torch.manual_seed(0)
-    w8 = any(ARMS[a].get("_w") == "fp8" for a in args.arms.split(","))
-    eng = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=120, max_prefill_tokens=32768,
-                    block_size=args.block_size, weight_dtype="fp8" if w8 else "bf16")
+    wds = []  # the weight dtypes the arms ask for, in order: one model (and engine) each
+    for a in args.arms.split(","):
+        if ARMS[a].get("_w") and ARMS[a]["_w"] not in wds:
+            wds.append(ARMS[a]["_w"])
+    primary = wds[0] if wds else "bf16"
+    kv_gb = 120 if len(wds) <= 1 else 60
+    eng = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=kv_gb, max_prefill_tokens=32768,
+                    block_size=args.block_size, weight_dtype=primary)
     eng.model.__class__ = tuned_model_class()  # same object, overridable stream choice
+    engs = {primary: eng}
+    for wd in wds[1:]:
+        engs[wd] = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=kv_gb,
+                             max_prefill_tokens=32768, block_size=args.block_size, weight_dtype=wd)
+        engs[wd].model.__class__ = tuned_model_class()
     g = torch.Generator().manual_seed(1)
     sp = SamplingParams(max_new_tokens=6000, ignore_eos=True)
     prompts = [torch.randint(0, 128000, (args.prompt + int(torch.randint(-100, 100, (1,), generator=g)),),
@@ -167,12 +183,15 @@ def main():
     base_part, base_spart = eng.long_part_size, eng.part_size
     base_groups = dict(eng.model.proj_group)
     base_ring = ops.native().stream_gemm_fp8_deep()
+    base_ring4 = ops.native().stream_gemm_mxfp4_deep()
     arms = args.arms.split(",")
     res = {a: [] for a in arms}
     for r in range(args.rounds):
         for a in arms:
             spec = dict(ARMS[a])
-            eng = eng8 if spec.get("_kv") == "fp8" else eng16  # (restart() and the steps below follow it)
+            # (restart() and the steps below follow it; the FP8-KV engine shares the first model)
+            eng = eng8 if spec.get("_kv") == "fp8" else engs.get(spec.get("_w"), eng16)
+            assert eng.model.weight_dtype == spec.get("_w", primary), "this arm's weights are not this engine's"
             restart()
             eng.model.overrides = {k: v for k, v in spec.items() if not k.startswith("_")}
             eng.long_part_size = spec.get("_part", base_part)
@@ -190,7 +209,9 @@ def main():
             eng.model.STREAM_CFG_RES16 = spec.get("_res_cfg", type(eng.model).STREAM_CFG_RES16)
             ops.native().stream_gemm_set_slice_xcd(spec.get("_slice_xcd", 0))
             eng.model.fp8_stream = spec.get("_w") == "fp8"
-            ops.native().stream_gemm_fp8_set_deep(spec.get("_ring", base_ring))
+            eng.model.mxfp4_stream = spec.get("_w") == "mxfp4" and not spec.get("_stream_off")
+            ops.native().stream_gemm_fp8_set_deep(spec.get("_ring", base_ring) if spec.get("_w") == "fp8" else base_ring)
+            ops.native().stream_gemm_mxfp4_set_deep(spec.get("_ring", base_ring4) if spec.get("_w") == "mxfp4" else base_ring4)
             eng.model.slab_bf16 = spec.get("_slab16", type(eng.model).slab_bf16)
             for n, g in {**base_groups, **spec.get("_groups", {})}.items():
                 eng.model.set_proj_group(n, g)

@@ -191,6 +191,67 @@ def stream_fp8_sweep(Ms=(1, 16, 64, 128, 256), rounds=3):
             del w16, w8
 
 
+def stream_mxfp4_sweep(Ms=(1, 16, 64, 128, 256), rounds=3):
+    """MXFP4 weights (W4A16) against FP8 and bf16 on the streaming decode GEMM, shaped like
+    ``stream_fp8_sweep``: the four Llama-3-8B projections at decode batch M at the configuration,
+    K-slices, output form and weight group the decoder dispatches, cold weights.  Arms, alternating
+    round by round: the bf16 kernel (on the MXFP4-dequantised weights), the FP8 arm (its default
+    ring), the MXFP4 arm with the bf16 configuration's ring stages (``mxfp4``) and with twice that
+    (``mxfp4_deep``).  TB/s counts the weight bytes each arm streams (MXFP4: codes + scale bytes)."""
+    from django_assistant_bot_amd.models.llama import LlamaModel
+
+    nat = ops.native()
+    shapes = (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    for M in Ms:
+        for name, N, K in shapes:
+            cfg = LlamaModel._stream_cfg(LlamaModel, name, M, N)
+            if cfg < 0 or not nat.stream_gemm_mxfp4_ok(cfg):
+                emit(op=f"stream-mxfp4-{name}", M=M, cfg=cfg, note="not streamed / no MXFP4 arm at this batch")
+                continue
+            S = 1 if name == "gate_up" else LlamaModel._stream_splits(N, K, nat.stream_gemm_bn(cfg))
+            grp = LlamaModel.PROJ_GROUPS.get(name, 1)
+            epi = ops.EPI_SWIGLU8 if name == "gate_up" else ops.EPI_NONE
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            ncopy = max(2, int(2.5e9 // (N * K * 2)) + 1)
+            w16, w8, w4 = [], [], []
+            for _ in range(ncopy):
+                w = (torch.randn(N, K, device="cuda") * 0.02).to(torch.bfloat16)
+                codes, scales = ops.weight_quantize_mxfp4(w)
+                w16.append(ops.shuffle_weights(ops.weight_dequantize_mxfp4(codes, scales), grp))
+                w4.append((ops.shuffle_weights_mxfp4(codes, grp), ops.shuffle_scales_mxfp4(scales)))
+                data, exps = ops.weight_quantize_fp8(w)
+                w8.append((ops.shuffle_weights_fp8(data, grp), exps))
+                del w, codes, scales, data
+            out = (torch.empty((S, M, N), dtype=torch.bfloat16, device="cuda") if S > 1 else
+                   torch.empty((M, N // 2 if epi else N), dtype=torch.bfloat16, device="cuda"))
+            kw = dict(splits=S, epilogue=epi, out=out, nt=True, cfg=cfg, w_group=grp, slab_dtype=torch.bfloat16)
+
+            def run_mx(deep):
+                nat.stream_gemm_mxfp4_set_deep(deep)  # (read at launch: baked into the captured graph)
+                return graph_time([lambda w=w, s=s: ops.stream_gemm(a, w, w_scales=s, **kw) for w, s in w4])
+
+            arms = {"bf16": lambda: graph_time([lambda w=w: ops.stream_gemm(a, w, **kw) for w in w16]),
+                    "fp8": lambda: graph_time([lambda w=w, e=e: ops.stream_gemm(a, w, w_exps=e, **kw) for w, e in w8]),
+                    "mxfp4": lambda: run_mx(0), "mxfp4_deep": lambda: run_mx(1)}
+            times = {k: [] for k in arms}
+            deep0 = nat.stream_gemm_mxfp4_deep()
+            for _ in range(rounds):
+                for k, fn in arms.items():
+                    times[k].append(fn())
+            nat.stream_gemm_mxfp4_set_deep(deep0)
+            res = {"op": f"stream-mxfp4-{name}", "M": M, "N": N, "K": K, "cfg": cfg, "S": S, "group": grp}
+            mxb = N * K // 2 + N * K // 32
+            for k, byts in (("bf16", 2 * N * K), ("fp8", N * K + N), ("mxfp4", mxb), ("mxfp4_deep", mxb)):
+                t = sorted(times[k])[len(times[k]) // 2]
+                res[f"{k}_us"] = round(t * 1e6, 1)
+                res[f"{k}_tbps"] = round(byts / t / 1e12, 2)
+                res[f"{k}_us_min_max"] = [round(min(times[k]) * 1e6, 1), round(max(times[k]) * 1e6, 1)]
+            for k in ("fp8", "mxfp4", "mxfp4_deep"):
+                res[f"{k}_vs_bf16"] = round(res[f"{k}_us"] / res["bf16_us"], 3)
+            emit(**res)
+            del w16, w8, w4
+
+
 def attn_suite():
     # prefill: 16 sequences x 1024 tokens, Llama-3-8B heads
     B, T, Hq, Hkv, D, bs = 16, 1024, 32, 8, 128, 64
@@ -461,6 +522,8 @@ if __name__ == "__main__":
                      tuple(int(m) for m in sys.argv[3].split(",")) if len(sys.argv) > 3 else (128,))
     if which == "stream_fp8":
         stream_fp8_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (1, 16, 64, 128, 256))
+    if which == "stream_mxfp4":
+        stream_mxfp4_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (1, 16, 64, 128, 256))
     if which == "decode":
         decode_sweep()
     if which in ("decode", "decodefp8"):

@@ -313,6 +313,20 @@ PYBIND11_MODULE(_native, m) {
   m.def("stream_gemm_fp8_nwin", &dab::stream_gemm_fp8_nwin);
   m.def("stream_gemm_fp8_set_deep", &dab::stream_gemm_fp8_set_deep);
   m.def("stream_gemm_fp8_deep", &dab::stream_gemm_fp8_deep);
+  m.def("stream_gemm_mxfp4", [](u X, long ldx, u W, u w_scales, u out, long ldo, u residual, long ldr, int M, int N,
+                                int K, int S, int epilogue, u s, int nt, int cfg, float norm_eps, int slab_bf16,
+                                int w_group) {
+    check(dab::stream_gemm_mxfp4(CVP(X), ldx, CVP(W), CVP(w_scales), VP(out), ldo, CVP(residual), ldr, M, N, K, S,
+                                 epilogue, ST(s), nt, cfg, norm_eps, slab_bf16, w_group),
+          "stream_gemm_mxfp4");
+  }, py::arg("X"), py::arg("ldx"), py::arg("W"), py::arg("w_scales"), py::arg("out"), py::arg("ldo"),
+     py::arg("residual"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("S"), py::arg("epilogue"),
+     py::arg("s"), py::arg("nt"), py::arg("cfg"), py::arg("norm_eps") = 0.f, py::arg("slab_bf16") = 0,
+     py::arg("w_group") = 1);
+  m.def("stream_gemm_mxfp4_ok", &dab::stream_gemm_mxfp4_ok);
+  m.def("stream_gemm_mxfp4_nwin", &dab::stream_gemm_mxfp4_nwin);
+  m.def("stream_gemm_mxfp4_set_deep", &dab::stream_gemm_mxfp4_set_deep);
+  m.def("stream_gemm_mxfp4_deep", &dab::stream_gemm_mxfp4_deep);
   m.def("stream_gemm_bn", &dab::stream_gemm_bn);
   m.def("stream_gemm_max_m", &dab::stream_gemm_max_m);
   m.def("stream_gemm_set_slice_xcd", &dab::stream_gemm_set_slice_xcd);

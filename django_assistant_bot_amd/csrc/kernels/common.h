@@ -131,6 +131,18 @@ __device__ __forceinline__ bf16x8 fp8x8_bf16(uint32_t lo, uint32_t hi) {
 
 __device__ __forceinline__ float exp_scale(uint32_t b) { return __uint_as_float(b << 23); }  // 2^(b - 127)
 
+// 8 e2m1 codes of one dword (byte i: k 2i in the low nibble, k 2i + 1 in the high one) times the
+// power-of-two scale `s` (exp_scale) -> 8 bf16 in ascending k (v_cvt_scalef32_pk_bf16_fp4 per byte)
+template <int B>
+__device__ __forceinline__ uint32_t fp4x2_bf16(uint32_t w, float s) {
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, B));
+}
+
+__device__ __forceinline__ bf16x8 fp4x8_bf16(uint32_t w, float s) {
+  const u32x4 r = {fp4x2_bf16<0>(w, s), fp4x2_bf16<1>(w, s), fp4x2_bf16<2>(w, s), fp4x2_bf16<3>(w, s)};
+  return __builtin_bit_cast(bf16x8, r);
+}
+
 // 16 e4m3fn bytes times the row's scale `s` (exp_scale) -> 16 bf16 in byte order: o[0] bytes 0 - 7,
 // o[1] bytes 8 - 15 (the dequantisers of the KV cache and of the index)
 __device__ __forceinline__ void fp8x16_dequant(const u32x4& d, float s, u32x4 (&o)[2]) {

@@ -135,6 +135,18 @@ int stream_gemm_fp8_nwin(int cfg);  // weight-ring stages of cfg's FP8 arm at th
 // FP8 arm ring depth: 0 = the bf16 configuration's, 1 = twice that (the same ring registers); A/B switch
 void stream_gemm_fp8_set_deep(int on);
 int stream_gemm_fp8_deep();
+// ... with MXFP4 weights (W4A16): W = e2m1 codes, two per byte, in the ops.shuffle_weights_mxfp4 layout
+// (16-byte aligned), w_scales = one E8M0 byte per 32 k of a row in the ops.shuffle_scales_mxfp4 layout
+// (4-byte aligned).  The same numbers as stream_gemm on the dequantised weights.  K % 128, a null or
+// misaligned W / w_scales or a cfg without an MXFP4 instantiation (stream_gemm_mxfp4_ok) -> hipErrorInvalidValue
+int stream_gemm_mxfp4(const void* X, long ldx, const void* W, const void* w_scales, void* out, long ldo,
+                      const void* residual, long ldr, int M, int N, int K, int S, int epilogue, hipStream_t s,
+                      int nt_weights, int cfg, float norm_eps = 0.f, int slab_bf16 = 0, int w_group = 1);
+int stream_gemm_mxfp4_ok(int cfg);    // 1: cfg has an MXFP4-weight instantiation
+int stream_gemm_mxfp4_nwin(int cfg);  // weight-ring stages of cfg's MXFP4 arm at the current ring mode (0: none)
+// MXFP4 arm ring depth: 0 = the bf16 configuration's stages, 1 = twice that; A/B switch
+void stream_gemm_mxfp4_set_deep(int on);
+int stream_gemm_mxfp4_deep();
 // fp32 (or bf16: slab_bf16) split-K slabs [S][M][N] -> bf16 [M, N] (+ residual)
 int slab_reduce(void* out, long ldo, const void* slabs, int S, int M, int N, const void* residual, long ldr,
                 hipStream_t s, int slab_bf16 = 0);

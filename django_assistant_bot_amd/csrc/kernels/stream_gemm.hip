@@ -69,6 +69,14 @@ struct StreamParams8 : StreamParams {
   const uint8_t* w_exps;  // one E8M0 exponent byte per weight row [N] (W = e4m3fn bytes)
 };
 
+// MXFP4-weight arm (W = e2m1 codes, two per byte)
+struct StreamParams4 : StreamParams {
+  const uint8_t* w_scales;  // one E8M0 scale byte per 32 k of a row, shuffle_scales_mxfp4 layout
+};
+
+// weight formats of stream_gemm_kernel
+constexpr int WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2;
+
 constexpr int ST_EPI_NONE = 0, ST_EPI_SWIGLU = 2, ST_EPI_SWIGLU8 = 4, ST_EPI_CAND = 8;
 
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
@@ -92,6 +100,17 @@ __device__ __forceinline__ bool static_for(F&& f) {
   return true;
 }
 
+// The MXFP4 arm's scale ring (empty in the other arms): the descriptor over the scale bytes, each row
+// tile's byte offset at the K-slice's first stage, and one dword per ring slot and row tile
+template <bool ON, int NWIN, int RT>
+struct ScaleRing {};
+template <int NWIN, int RT>
+struct ScaleRing<true, NWIN, RT> {
+  __amdgpu_buffer_rsrc_t res;
+  int blk[RT];
+  uint32_t v[NWIN][RT];
+};
+
 // ABL (benchmark ablations only): 1 no X staging, 2 no MFMA, 3 weight stream only (no X, no LDS
 // reads, no MFMA), 4 no split-K slab stores, 5 the weight addressing of a tile-interleaved fragment
 // layout (the full kernel on the wrong bytes: what that layout's access pattern would cost); results
@@ -108,10 +127,24 @@ __device__ __forceinline__ bool static_for(F&& f) {
 // power-of-two exponents multiply the fp32 sums once, in tile4.  Every dequantised weight is
 // bf16-exact and a power of two commutes with every rounding, so the result equals, bit for bit,
 // the bf16 kernel's on the dequantised weights (same operand and summation order).
+//
+// WF_MXFP4 (MXFP4 weights, W4A16): W is the shuffle_weights_mxfp4 copy [N/16][K/128][64 lanes]
+// [16 B] of e2m1 codes (lane l = row l & 15; bytes 4c..4c+3 the 8 codes of k 128j + 32c + 8(l>>4)..,
+// the lower k in the low nibble), so one 16-B lane load (still a 1 KB wave read) feeds the four
+// 32-deep MFMA chunks of a stage: a ring slot holds a quarter of the registers.  A chunk of a row is
+// one MX block: the block's E8M0 scale byte travels in the same ring, one dword per lane, row tile
+// and stage (shuffle_scales_mxfp4: [N/16][K/128][16 rows][4 B], lane l reads row l & 15), and is
+// applied by the conversion (v_cvt_scalef32_pk_bf16_fp4, exact) -- it varies along K, so it cannot
+// wait for the fp32 sums.  The MFMA operands are the dequantised weights themselves, in the bf16
+// kernel's order: the result is bit-equal to the bf16 kernel's on them.  KG = 2 (64 k per wave and
+// stage): k-group kg takes chunks 2kg, 2kg + 1 of every fragment with one 8-B lane load (bytes
+// 8kg .. 8kg + 7 of the lane's 16; the two k-groups' loads cover the 1 KB) and their two scale bytes
+// with one 2-B load, so every code and scale byte is still read once.
 template <int MT, int RT, int KG, int KS, int NB, int NWIN, int NL, bool SHUF, bool NT_W, int ABL = 0, int NWC = 4,
-          bool W8 = false>
+          int WF = WF_BF16>
 __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
-    std::conditional_t<W8, StreamParams8, StreamParams> p) {
+    std::conditional_t<WF == WF_MXFP4, StreamParams4, std::conditional_t<WF == WF_FP8, StreamParams8, StreamParams>> p) {
+  constexpr bool W8 = WF == WF_FP8, W4 = WF == WF_MXFP4;
   constexpr int RG = NWC / KG;        // row groups
   constexpr int BN = 16 * RT * RG;    // weight rows per workgroup
   constexpr int BNP = BN <= 64 ? 64 : BN <= 128 ? 128 : 256;  // epilogue tile row stride (XOR swizzle range)
@@ -123,10 +156,13 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
   constexpr int GPL = GPS / NL;       // ... per loader wave
   constexpr int KW = KS / KG;         // k per compute wave per stage
   constexpr int CPW = KW / 32;        // 32-deep MFMA chunks per wave per stage
-  constexpr int WK = W8 ? 64 : 32;            // k per 1 KB weight fragment (SHUF)
-  constexpr int EB = W8 ? 1 : 2;              // bytes per weight
-  constexpr int LPW = W8 ? CPW / 2 : CPW;     // 16-B weight loads per wave, row tile and stage
+  constexpr int WK = W4 ? 128 : W8 ? 64 : 32;  // k per 1 KB weight fragment (SHUF)
+  constexpr int EB = W8 ? 1 : 2;               // bytes per weight (MXFP4: half a byte, its own terms below)
+  constexpr int CPL = W4 ? WK / 32 / KG : WK / 32;  // 32-deep MFMA chunks per weight load (16 B; W4, KG 2: 8 B)
+  constexpr int LPW = CPW / CPL;               // 16-B weight loads per wave, row tile and stage
   static_assert(!W8 || (SHUF && ABL == 0 && CPW % 2 == 0), "FP8 weights: fragment layout, whole 64-deep steps");
+  static_assert(!W4 || (SHUF && ABL == 0 && (KG == 1 || KG == 2) && CPW == CPL),
+                "MXFP4 weights: fragment layout, one 128-deep fragment per stage over the k-groups");
   constexpr int RED = KG * MP * BNP * 4;
   static_assert(BN <= 256 && BN % 16 == 0, "tile rows");
   // + per-row scales of the consumer RMSNorm and each wave's per-row sums of squares (after the ring
@@ -203,15 +239,17 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
     // block offsets are then absolute (descriptor over the whole copy) and a k chunk is G KB on
     const bool grp = SHUF && p.wgrp > 1;
     const auto wres = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.W + (grp ? 0 : (size_t)n0 * p.ldw * EB)), 0,
-        grp ? (int)((long)p.N * p.K * EB) : (int)(w_rows * p.ldw * EB), 0x00020000);
+        (void*)((const char*)p.W + (grp ? 0 : (W4 ? (size_t)n0 * p.ldw / 2 : (size_t)n0 * p.ldw * EB))), 0,
+        grp ? (int)(W4 ? (long)p.N * p.K / 2 : (long)p.N * p.K * EB)
+            : (int)(W4 ? w_rows * p.ldw / 2 : w_rows * p.ldw * EB),
+        0x00020000);
     const int cstride = SHUF ? (grp ? p.wgrp : 1) * 1024 : 0;  // bytes per WK-deep k chunk (SHUF)
     // row-major W: lane (li, g) reads row li, k 8g..8g+7 of a 16 x 32 chunk (16 rows x 64 B per load);
     // SHUF (shuffle_weights layout [N/16][K/32][64 lanes][8]): every load is 1 KB contiguous
     const int w_voff = SHUF ? lane * 16 + ((k_begin + kg * KW) / WK) * cstride
                             : (int)(((16 * RT * rg + li) * p.ldw + k_begin + kg * KW + 8 * g) * 2);
-    const int a_stride = SHUF ? p.K * 16 * EB : 16 * (int)p.ldw * 2;
-    const int w_rowtile0 = SHUF ? RT * rg * p.K * 16 * EB : 0;
+    const int a_stride = SHUF ? (W4 ? p.K * 8 : p.K * 16 * EB) : 16 * (int)p.ldw * 2;
+    const int w_rowtile0 = SHUF ? (W4 ? RT * rg * p.K * 8 : RT * rg * p.K * 16 * EB) : 0;
     // SHUF: byte offset of row block (RT rg + a) of the tile at k chunk 0
     int wblk[RT];
 #pragma unroll
@@ -223,7 +261,15 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
         wblk[a] = a * a_stride + w_rowtile0;
       }
     }
-    bf16x8 wr[NWIN][RT][LPW];  // (W8: 16 e4m3fn bytes, two chunks)
+    bf16x8 wr[NWIN][RT][LPW];  // (W8: 16 e4m3fn bytes, two chunks; W4: 32 e2m1 codes, four chunks, or 16, two)
+    // W4: the chunks' scale bytes of the lane's row ride in the same ring, chunk c's in byte c (a
+    // descriptor over all of them: block offsets absolute, K/2 bytes per 16-row block, 64 per 128-deep stage)
+    ScaleRing<W4, NWIN, RT> sc;
+    if constexpr (W4) {
+      sc.res = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_scales, 0, (int)((long)p.N * p.K / 32), 0x00020000);
+#pragma unroll
+      for (int a = 0; a < RT; ++a) sc.blk[a] = (n0 / 16 + RT * rg + a) * (p.K / 2) + (k_begin / 128) * 64;
+    }
     // clamped past the slice end: the ring keeps a branch-free load stream, so the compiler's
     // in-order vmcnt count stays exact (the spare loads re-read the last stage from L2)
     auto load_w = [&](int slot, int st, int a, int c) DAB_INLINE {
@@ -234,10 +280,20 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
         const int chunk = (k_begin + kg * KW) / 32 + min(st, nst - 1) * (KS / 32) + c;
         const int off = (chunk * (BN / 16) + RT * rg + a) * 1024 + lane * 16;
         wr[slot][a][c] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wres, off, 0, NT_W ? 2 : 0));
+      } else if constexpr (W4 && KG == 2) {
+        // this k-group's half of the lane's 16 bytes (chunks 2kg, 2kg + 1) and its two scale bytes
+        const int soff = min(st, nst - 1) * cstride + wblk[a];
+        const u32x2 v = __builtin_bit_cast(
+            u32x2, __builtin_amdgcn_raw_buffer_load_b64(wres, w_voff + 8 * kg, soff, NT_W ? 2 : 0));
+        wr[slot][a][c] = __builtin_bit_cast(bf16x8, u32x4{v[0], v[1], 0u, 0u});
+        sc.v[slot][a] = (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(sc.res, li * 4 + 2 * kg,
+                                                                       min(st, nst - 1) * 64 + sc.blk[a], 0);
       } else if constexpr (SHUF) {
         const int soff = min(st, nst - 1) * (KS / WK) * cstride + wblk[a];
         wr[slot][a][c] = __builtin_bit_cast(
             bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wres, w_voff + cstride * c, soff, NT_W ? 2 : 0));
+        if constexpr (W4)
+          sc.v[slot][a] = __builtin_amdgcn_raw_buffer_load_b32(sc.res, li * 4, min(st, nst - 1) * 64 + sc.blk[a], 0);
       } else {
         const int soff = min(st, nst - 1) * KS * 2 + a * a_stride + w_rowtile0;
         wr[slot][a][c] = __builtin_bit_cast(
@@ -281,14 +337,19 @@ __global__ __launch_bounds__(64 * (NWC + NL), 1) void stream_gemm_kernel(
             const bf16x8 wa = (c & 1) ? fp8x8_bf16(b8[2], b8[3]) : fp8x8_bf16(b8[0], b8[1]);
 #pragma unroll
             for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wa, bx[t], acc[a][t]);
+          } else if constexpr (W4) {
+            const u32x4 b4 = __builtin_bit_cast(u32x4, wr[h][a][0]);
+            const bf16x8 wa = fp4x8_bf16(b4[c], exp_scale((sc.v[h][a] >> (8 * c)) & 0xff));
+#pragma unroll
+            for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wa, bx[t], acc[a][t]);
           } else {
 #pragma unroll
             for (int t = 0; t < MT; ++t) acc[a][t] = mfma16(wr[h][a][c], bx[t], acc[a][t]);
           }
-          if constexpr (!W8)
+          if constexpr (CPL == 1)
             load_w(h, st + NWIN, a, c);
-          else if (c & 1)  // (unrolled: static) both halves of the 16 bytes are consumed
-            load_w(h, st + NWIN, a, c / 2);
+          else if (c % CPL == CPL - 1)  // (unrolled: static) every chunk of the 16 bytes is consumed
+            load_w(h, st + NWIN, a, c / CPL);
           // keep the reload right behind its MFMAs (the scheduler would otherwise sink every
           // reload to the stage end and halve the bytes in flight)
           __builtin_amdgcn_sched_barrier(0);
@@ -543,29 +604,33 @@ static void launch_cfg(const StreamParams& p, hipStream_t s, bool nt) {
 // (LlamaModel._stream_cfg, STREAM_WIDE["gate_up"], STREAM_CFG_RES16).  DEEP: twice the weight-ring
 // stages of the bf16 configuration, i.e. the same ring registers and bytes in flight.
 constexpr bool fp8_cfg(int c) { return c == 10 || c == 13 || c == 20 || c == 27 || c == 30 || c == 31 || c == 32; }
+// MXFP4-weight instantiations: the same set (cfg 27, KG = 2, with 8-byte lane loads).  DEEP: twice the
+// weight-ring stages of the bf16 configuration, i.e. half its ring bytes in flight.
+constexpr bool mxfp4_cfg(int c) { return fp8_cfg(c); }
 
-template <int C, bool DEEP>
-static void launch_cfg_fp8(const StreamParams8& p, hipStream_t s, bool nt) {
+// the FP8 / MXFP4 arm of configuration C (P: StreamParams8 / StreamParams4)
+template <int C, bool DEEP, int WF, typename P>
+static void launch_cfg_q(const P& p, hipStream_t s, bool nt) {
   constexpr StreamCfg c = kStreamCfgs[C];
   constexpr int nwin = c.nwin * (DEEP ? 2 : 1);
   const int bn = 16 * c.rt * (c.nwc / c.kg);
   const dim3 grid((p.N / bn) * p.S), block(64 * (c.nwc + c.nl));
   if (nt)
-    hipLaunchKernelGGL((stream_gemm_kernel<c.mt, c.rt, c.kg, 128, c.nb, nwin, c.nl, true, true, 0, c.nwc, true>), grid,
+    hipLaunchKernelGGL((stream_gemm_kernel<c.mt, c.rt, c.kg, 128, c.nb, nwin, c.nl, true, true, 0, c.nwc, WF>), grid,
                        block, 0, s, p);
   else
-    hipLaunchKernelGGL((stream_gemm_kernel<c.mt, c.rt, c.kg, 128, c.nb, nwin, c.nl, true, false, 0, c.nwc, true>), grid,
+    hipLaunchKernelGGL((stream_gemm_kernel<c.mt, c.rt, c.kg, 128, c.nb, nwin, c.nl, true, false, 0, c.nwc, WF>), grid,
                        block, 0, s, p);
 }
 
-template <int C = 0>
-static void launch_any_fp8(int cfg, const StreamParams8& p, hipStream_t s, bool nt, bool deep) {
+template <int WF, int C = 0, typename P>
+static void launch_any_q(int cfg, const P& p, hipStream_t s, bool nt, bool deep) {
   if constexpr (C < kNumStreamCfgs) {
-    if constexpr (fp8_cfg(C)) {
-      static_assert(kStreamCfgs[C].shuf && kStreamCfgs[C].abl == 0, "FP8 arm: fragment-layout configurations");
-      if (cfg == C) return deep ? launch_cfg_fp8<C, true>(p, s, nt) : launch_cfg_fp8<C, false>(p, s, nt);
+    if constexpr (WF == WF_MXFP4 ? mxfp4_cfg(C) : fp8_cfg(C)) {
+      static_assert(kStreamCfgs[C].shuf && kStreamCfgs[C].abl == 0, "FP8 / MXFP4 arm: fragment-layout configurations");
+      if (cfg == C) return deep ? launch_cfg_q<C, true, WF>(p, s, nt) : launch_cfg_q<C, false, WF>(p, s, nt);
     }
-    launch_any_fp8<C + 1>(cfg, p, s, nt, deep);
+    launch_any_q<WF, C + 1>(cfg, p, s, nt, deep);
   }
 }
 
@@ -594,7 +659,7 @@ static int g_slice_xcd = [] {
 void stream_gemm_set_slice_xcd(int on) { g_slice_xcd = on; }
 int stream_gemm_slice_xcd() { return g_slice_xcd; }
 
-// FP8 arm ring depth (A/B; DAB_STREAM_FP8_DEEP): see launch_cfg_fp8
+// FP8 arm ring depth (A/B; DAB_STREAM_FP8_DEEP): see launch_cfg_q
 static int g_fp8_deep = [] {
   const char* e = std::getenv("DAB_STREAM_FP8_DEEP");
   return e ? std::atoi(e) != 0 : 0;
@@ -604,8 +669,22 @@ int stream_gemm_fp8_deep() { return g_fp8_deep; }
 int stream_gemm_fp8_ok(int cfg) { return cfg >= 0 && cfg < kNumStreamCfgs && fp8_cfg(cfg); }
 int stream_gemm_fp8_nwin(int cfg) { return stream_gemm_fp8_ok(cfg) ? kStreamCfgs[cfg].nwin * (g_fp8_deep ? 2 : 1) : 0; }
 
-// w_exps == nullptr: bf16 weights (row stride ldw); else the FP8 fragment copy + row exponents
-static int stream_gemm_any(const void* X, long ldx, const void* W, long ldw, const uint8_t* w_exps, void* out, long ldo,
+// MXFP4 arm ring depth (A/B; DAB_STREAM_MXFP4_DEEP): see mxfp4_cfg
+static int g_mxfp4_deep = [] {
+  const char* e = std::getenv("DAB_STREAM_MXFP4_DEEP");
+  return e ? std::atoi(e) != 0 : 0;
+}();
+void stream_gemm_mxfp4_set_deep(int on) { g_mxfp4_deep = on != 0; }
+int stream_gemm_mxfp4_deep() { return g_mxfp4_deep; }
+int stream_gemm_mxfp4_ok(int cfg) { return cfg >= 0 && cfg < kNumStreamCfgs && mxfp4_cfg(cfg); }
+int stream_gemm_mxfp4_nwin(int cfg) {
+  return stream_gemm_mxfp4_ok(cfg) ? kStreamCfgs[cfg].nwin * (g_mxfp4_deep ? 2 : 1) : 0;
+}
+
+// w_exps == w_scales == nullptr: bf16 weights (row stride ldw); w_exps: the FP8 fragment copy + row
+// exponents; w_scales: the MXFP4 fragment copy + block scales
+static int stream_gemm_any(const void* X, long ldx, const void* W, long ldw, const uint8_t* w_exps,
+                           const uint8_t* w_scales, void* out, long ldo,
                            const void* residual, long ldr, int M, int N, int K, int S, int epilogue, hipStream_t s,
                            int nt_weights, int cfg, float norm_eps, int slab_bf16, int w_group) {
   constexpr int KS = 128;
@@ -617,8 +696,9 @@ static int stream_gemm_any(const void* X, long ldx, const void* W, long ldw, con
   if (epilogue == ST_EPI_SWIGLU && bn % 32) return hipErrorInvalidValue;  // whole 16 + 16 row pairs per tile
   if (S > 1 && (epilogue != ST_EPI_NONE || residual)) return hipErrorInvalidValue;
   if (residual && ldr % 8) return hipErrorInvalidValue;
-  const long eb = w_exps ? 1 : 2;  // bytes per weight
+  const long eb = w_exps ? 1 : 2;  // bytes per weight (an upper bound under MXFP4)
   if ((long)bn * ldw * eb >= (1L << 31)) return hipErrorInvalidValue;  // buffer descriptor range
+  if (w_scales && (long)N * K / 32 >= (1L << 31)) return hipErrorInvalidValue;
   if (kStreamCfgs[cfg].shuf && (ldw != K || K % 32)) return hipErrorInvalidValue;
   StreamParams p{};
   p.X = (const bf16*)X;
@@ -645,8 +725,10 @@ static int stream_gemm_any(const void* X, long ldx, const void* W, long ldw, con
   if (p.wgrp > 1 && (!kStreamCfgs[cfg].shuf || N % (16 * p.wgrp) || (long)N * K * eb >= (1L << 31)))
     return hipErrorInvalidValue;
   if (p.norm && (residual || K % 8 || M > stream_gemm_max_m(cfg))) return hipErrorInvalidValue;
-  if (w_exps)
-    launch_any_fp8(cfg, StreamParams8{p, w_exps}, s, nt_weights != 0, g_fp8_deep != 0);
+  if (w_scales)
+    launch_any_q<WF_MXFP4>(cfg, StreamParams4{p, w_scales}, s, nt_weights != 0, g_mxfp4_deep != 0);
+  else if (w_exps)
+    launch_any_q<WF_FP8>(cfg, StreamParams8{p, w_exps}, s, nt_weights != 0, g_fp8_deep != 0);
   else
     launch_any(cfg, p, s, nt_weights != 0);
   return hipGetLastError();
@@ -655,8 +737,8 @@ static int stream_gemm_any(const void* X, long ldx, const void* W, long ldw, con
 int stream_gemm(const void* X, long ldx, const void* W, long ldw, void* out, long ldo, const void* residual, long ldr,
                 int M, int N, int K, int S, int epilogue, hipStream_t s, int nt_weights, int cfg, float norm_eps,
                 int slab_bf16, int w_group) {
-  return stream_gemm_any(X, ldx, W, ldw, nullptr, out, ldo, residual, ldr, M, N, K, S, epilogue, s, nt_weights, cfg,
-                         norm_eps, slab_bf16, w_group);
+  return stream_gemm_any(X, ldx, W, ldw, nullptr, nullptr, out, ldo, residual, ldr, M, N, K, S, epilogue, s, nt_weights,
+                         cfg, norm_eps, slab_bf16, w_group);
 }
 
 int stream_gemm_fp8(const void* X, long ldx, const void* W, const void* w_exps, void* out, long ldo,
@@ -664,8 +746,18 @@ int stream_gemm_fp8(const void* X, long ldx, const void* W, const void* w_exps, 
                     int nt_weights, int cfg, float norm_eps, int slab_bf16, int w_group) {
   // (the exponents are read 4 rows at a time)
   if (K % 64 || !w_exps || (uintptr_t)w_exps % 4 || !stream_gemm_fp8_ok(cfg)) return hipErrorInvalidValue;
-  return stream_gemm_any(X, ldx, W, K, (const uint8_t*)w_exps, out, ldo, residual, ldr, M, N, K, S, epilogue, s,
+  return stream_gemm_any(X, ldx, W, K, (const uint8_t*)w_exps, nullptr, out, ldo, residual, ldr, M, N, K, S, epilogue, s,
                          nt_weights, cfg, norm_eps, slab_bf16, w_group);
+}
+
+int stream_gemm_mxfp4(const void* X, long ldx, const void* W, const void* w_scales, void* out, long ldo,
+                      const void* residual, long ldr, int M, int N, int K, int S, int epilogue, hipStream_t s,
+                      int nt_weights, int cfg, float norm_eps, int slab_bf16, int w_group) {
+  // (16-B lane loads of the codes, 4-B lane loads of the scales)
+  if (K % 128 || !W || (uintptr_t)W % 16 || !w_scales || (uintptr_t)w_scales % 4 || !stream_gemm_mxfp4_ok(cfg))
+    return hipErrorInvalidValue;
+  return stream_gemm_any(X, ldx, W, K, nullptr, (const uint8_t*)w_scales, out, ldo, residual, ldr, M, N, K, S, epilogue,
+                         s, nt_weights, cfg, norm_eps, slab_bf16, w_group);
 }
 
 // Sum S fp32 / bf16 slabs -> bf16 (optionally + residual), rounded like a bf16 GEMM output before the

@@ -123,8 +123,10 @@ class LLMEngine:
         the FP8 cache's bf16 prefill scratch (default: ``max(max_prefill_tokens, max_model_len) /
         block_size + max_batch`` blocks).
 
-        ``weight_dtype``: ``"bf16"`` or ``"fp8"`` (opt-in FP8 projection weights for the streaming
-        decode GEMM, ``LlamaModel(weight_dtype=...)``: docs/ARCHITECTURE.md "FP8 weights"); ``None``
+        ``weight_dtype``: ``"bf16"``, ``"fp8"`` (opt-in FP8 projection weights for the streaming
+        decode GEMM, ``LlamaModel(weight_dtype=...)``: docs/ARCHITECTURE.md "FP8 weights") or ``"mxfp4"``
+        (opt-in OCP MXFP4 projection weights, likewise: "MXFP4 weights"; TP 1, not with
+        ``fp8_weights_only``); ``None``
         reads ``DAB_WEIGHT_DTYPE`` from the environment, else bf16.  With ``shared_model`` the engine
         adopts the model's; a conflicting argument raises.
 
@@ -150,10 +152,10 @@ class LLMEngine:
         if fp8_weights_only is None:
             fp8_weights_only = parse_flag(os.environ.get("DAB_WEIGHT_FP8_ONLY"))
         fp8_weights_only = bool(fp8_weights_only)
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
-        if weight_dtype == "fp8" and tp_size > 1:
-            raise ValueError("weight_dtype='fp8' does not support tensor parallelism (tp_size > 1) yet")
+        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
+        if weight_dtype != "bf16" and tp_size > 1:
+            raise ValueError(f"weight_dtype={weight_dtype!r} does not support tensor parallelism (tp_size > 1) yet")
         if fp8_weights_only and weight_dtype != "fp8":
             raise ValueError("fp8_weights_only needs weight_dtype='fp8'")
         if fp8_weights_only and tp_size > 1:
@@ -251,8 +253,9 @@ class LLMEngine:
                       # the KV cache's element width (16: bf16, 8: fp8 = ``kv_cache_dtype``); a number like
                       # every other entry, since consumers subtract two snapshots of this dict
                       "kv_cache_bits": 8 if fp8 else 16,
-                      # the projection weights the decode GEMM streams (8: ``weight_dtype="fp8"``)
-                      "weight_bits": 8 if weight_dtype == "fp8" else 16,
+                      # the projection weights the decode GEMM streams (8: ``weight_dtype="fp8"``, 4:
+                      # ``"mxfp4"``, e2m1 codes; their block scales add a quarter of a bit)
+                      "weight_bits": {"fp8": 8, "mxfp4": 4}.get(weight_dtype, 16),
                       # whether the projections keep a bf16 copy (False: ``fp8_weights_only``), and the
                       # projection bytes resident, counted from the model's tensors
                       "weight_bf16_copy": not fp8_weights_only,

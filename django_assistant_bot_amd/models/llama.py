@@ -29,7 +29,8 @@ class DecoderLayer:
     """One layer's tensors.  On the GPU the four projections are held ONCE, in the
     ``ops.shuffle_weights`` fragment layout, which the decode GEMM (stream_gemm) streams and the
     prefill GEMMs (gemm256 / gemm_bt ``shuffled``) stage by LDS-DMA; on the CPU they are row-major.
-    Under ``weight_dtype="fp8"`` (GPU, fragment layout) each projection is an ``Fp8Proj``."""
+    Under ``weight_dtype="fp8"`` (GPU, fragment layout) each projection is an ``Fp8Proj``, under
+    ``weight_dtype="mxfp4"`` an ``Mxfp4Proj``."""
 
     attn_norm: torch.Tensor
     qkv_w: torch.Tensor
@@ -77,9 +78,43 @@ class Fp8Proj:
         self.group = group
 
 
+class Mxfp4Proj:
+    """One projection of a ``weight_dtype="mxfp4"`` decoder on the GPU, held twice: ``data`` / ``scales``,
+    the e2m1 codes in the ``ops.shuffle_weights_mxfp4`` layout and one E8M0 scale byte per 32 k of a
+    row in the ``ops.shuffle_scales_mxfp4`` layout, streamed by the decode GEMM (stream_gemm's MXFP4
+    arm), and ``w``, a bf16 ``ops.shuffle_weights`` copy of the DEQUANTISED values for the MFMA GEMMs
+    and every stream_gemm configuration without an MXFP4 arm.  Both hold the same numbers.
+    ``group``: the row-block group of the codes and of the bf16 copy (the scales have one layout)."""
+
+    __slots__ = ("w", "data", "scales", "group")
+
+    def __init__(self, w: torch.Tensor, data: torch.Tensor, scales: torch.Tensor, group: int = 1):
+        self.w, self.data, self.scales, self.group = w, data, scales, group
+
+    @classmethod
+    def from_rows(cls, codes: torch.Tensor, scales: torch.Tensor, group: int = 1) -> "Mxfp4Proj":
+        """From row-major codes [N, K/2] and scale bytes [N, K/32] (``ops.weight_quantize_mxfp4``)."""
+        w = ops.shuffle_weights(ops.weight_dequantize_mxfp4(codes, scales), group)
+        return cls(w, ops.shuffle_weights_mxfp4(codes, group), ops.shuffle_scales_mxfp4(scales), group)
+
+    @property
+    def shape(self):
+        return self.w.shape  # [N, K]
+
+    def nbytes(self) -> int:
+        """Bytes resident for this projection, counted from its tensors."""
+        return sum(t.numel() * t.element_size() for t in (self.w, self.data, self.scales))
+
+    def regroup(self, group: int) -> None:
+        """Re-lay both copies for ``group``, in place (pointers stay valid)."""
+        self.w.copy_(ops.shuffle_weights(ops.unshuffle_weights(self.w, self.group), group))
+        self.data.copy_(ops.shuffle_weights_mxfp4(ops.unshuffle_weights_mxfp4(self.data, self.group), group))
+        self.group = group
+
+
 def _bf16_copy(w):
-    """The bf16 tensor of a projection (a tensor, or an ``Fp8Proj``'s dequantised copy)."""
-    return w.w if isinstance(w, Fp8Proj) else w
+    """The bf16 tensor of a projection (a tensor, or an ``Fp8Proj``'s / ``Mxfp4Proj``'s dequantised copy)."""
+    return w.w if isinstance(w, (Fp8Proj, Mxfp4Proj)) else w
 
 
 @dataclass
@@ -228,6 +263,14 @@ class LlamaModel:
         wherever that one takes gemm256 or stream_gemm; elsewhere they differ in accumulation order only.
         On the CPU it changes nothing (the model already runs on dequantised row-major weights).
 
+        ``weight_dtype="mxfp4"`` (opt-in, TP 1, not with ``fp8_weights_only``): the same projections are
+        quantised at load time to OCP MXFP4 (``ops.weight_quantize_mxfp4``: e2m1 codes and one
+        power-of-two scale per 32 k of a row, 4.25 bits per weight) and the model computes with the
+        dequantised values everywhere.  On the GPU with the fragment layout and K % 128 == 0 each
+        projection is an ``Mxfp4Proj``: the decode GEMM streams the codes and scales wherever its
+        configuration has an MXFP4 arm, everything else reads a bf16 copy of the same values
+        (1.27x the bf16 model's projection memory).  Otherwise the weights are the dequantised tensors.
+
         ``consume``: the entries of ``weights`` are popped as the model takes them over, so each
         original is freed as soon as its fragment-layout copy exists (peak HBM = model + one
         tensor: 70B at TP 1 needs it, 2 x 140 GB would not fit in 288 GB).
@@ -238,10 +281,10 @@ class LlamaModel:
         samples from the all-gathered per-slice candidates (``ops.sample_candidates`` /
         ``sample_merge``).  Needs V % (32 tp) == 0 (whole JSON-mask words per slice); otherwise the
         head stays replicated."""
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
-        if weight_dtype == "fp8" and tp_size > 1:
-            raise ValueError("weight_dtype='fp8' is not supported under tensor parallelism (tp_size > 1)")
+        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
+        if weight_dtype != "bf16" and tp_size > 1:
+            raise ValueError(f"weight_dtype={weight_dtype!r} is not supported under tensor parallelism (tp_size > 1)")
         self.weight_dtype = weight_dtype
         self.fp8_weights_only = bool(fp8_weights_only)
         if self.fp8_weights_only:
@@ -293,6 +336,11 @@ class LlamaModel:
             """The decoder's one copy of projection ``name``: the fragment layout, grouped per
             ``PROJ_GROUPS`` where the shape allows (layer 0 decides for every layer)."""
             fp8 = self.weight_dtype == "fp8"
+            if self.weight_dtype == "mxfp4":
+                codes, scales = ops.weight_quantize_mxfp4(t)
+                if not (self.frag and t.shape[1] % 128 == 0):
+                    t = ops.weight_dequantize_mxfp4(codes, scales).to(t.dtype)
+                    codes = None  # (no MXFP4 fragment layout: the dequantised values alone)
             if fp8:
                 data, exps = ops.weight_quantize_fp8(t)
             if not self.frag:
@@ -302,6 +350,8 @@ class LlamaModel:
                 self.proj_group[name] = g if (t.shape[0] % (16 * g) == 0 and t.numel() * 2 < (1 << 31)) else 1
             if fp8:
                 return Fp8Proj.from_rows(data, exps, self.proj_group[name], bf16_copy=not self.fp8_weights_only)
+            if self.weight_dtype == "mxfp4" and codes is not None:
+                return Mxfp4Proj.from_rows(codes, scales, self.proj_group[name])
             return ops.shuffle_weights(t, self.proj_group[name])
 
         def load(i, name, norm=None):
@@ -378,7 +428,7 @@ class LlamaModel:
         total = 0
         for L in self.layers:
             for w in (L.qkv_w, L.o_w, L.gate_up_w, L.down_w):
-                total += w.nbytes() if isinstance(w, Fp8Proj) else w.numel() * w.element_size()
+                total += w.nbytes() if isinstance(w, (Fp8Proj, Mxfp4Proj)) else w.numel() * w.element_size()
         return total
 
     def set_proj_group(self, name: str, group: int) -> None:
@@ -392,7 +442,7 @@ class LlamaModel:
             w = getattr(L, name + "_w")
             if w.shape[0] % (16 * group):
                 raise ValueError(f"{name}: {w.shape[0]} rows are not whole groups of {group}")
-            if isinstance(w, Fp8Proj):
+            if isinstance(w, (Fp8Proj, Mxfp4Proj)):
                 w.regroup(group)
             else:
                 w.copy_(ops.shuffle_weights(ops.unshuffle_weights(w, old), group))
@@ -514,9 +564,9 @@ class LlamaModel:
             if cfg >= 0:
                 sw, e = self._stream_w(w, name, cfg)
                 if epilogue != ops.EPI_NONE:
-                    return ops.stream_gemm(x, sw, epilogue=epilogue, nt=True, cfg=cfg, w_group=grp, w_exps=e)
+                    return ops.stream_gemm(x, sw, epilogue=epilogue, nt=True, cfg=cfg, w_group=grp, **e)
                 sd = torch.bfloat16 if (self.slab_bf16 and self.tp_size == 1 and not slab_f32) else torch.float32
-                out = ops.stream_gemm(x, sw, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp, w_exps=e)
+                out = ops.stream_gemm(x, sw, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp, **e)
                 return ops.slab_reduce(out) if (s > 1 and not allow_slabs) else out
         return self._mfma(x, w, epilogue=epilogue, shuffled=self.frag, b_group=grp)
 
@@ -532,17 +582,27 @@ class LlamaModel:
     FP8_STREAM_OFF: frozenset = frozenset()
     fp8_stream = True  # off: every stream_gemm call reads the bf16 copies (benchmarks/decode_ab.py A/B)
 
+    # MXFP4 weights: the same opt-out (profiles/weight_mxfp4.md)
+    MXFP4_STREAM_OFF: frozenset = frozenset()
+    mxfp4_stream = True  # off: every stream_gemm call reads the bf16 copies (benchmarks/decode_ab.py A/B)
+
     def _stream_w(self, w, name: str, cfg: int):
-        """(weights, row exponents or None) for a stream_gemm call at ``cfg``: the FP8 copy of an
-        ``Fp8Proj`` where the kernel has an FP8 arm for ``cfg``, else the bf16 copy (same values)."""
+        """(weights, stream_gemm keyword arguments) for a stream_gemm call at ``cfg``: the FP8 copy of
+        an ``Fp8Proj`` with ``w_exps`` (the MXFP4 copy of an ``Mxfp4Proj`` with ``w_scales``) where
+        the kernel has such an arm for ``cfg``, else the bf16 copy (same values) and nothing."""
+        if isinstance(w, Mxfp4Proj):
+            if (self.mxfp4_stream and ops.native().stream_gemm_mxfp4_ok(cfg)
+                    and (name, cfg) not in self.MXFP4_STREAM_OFF):
+                return w.data, {"w_scales": w.scales}
+            return w.w, {}
         if not isinstance(w, Fp8Proj):
-            return w, None
+            return w, {}
         if self.fp8_stream and ops.native().stream_gemm_fp8_ok(cfg) and (name, cfg) not in self.FP8_STREAM_OFF:
-            return w.data, w.exps
+            return w.data, {"w_exps": w.exps}
         if w.w is None:
             raise RuntimeError(f"fp8_weights_only: stream_gemm cfg {cfg} ({name}) has no FP8 arm (or FP8 streaming "
                                "was switched off) and there is no bf16 copy to stream")
-        return w.w, None
+        return w.w, {}
 
     # Pure prefill steps whose caller reads only ``out_rows`` (the last token of each finished
     # prompt, ~30 rows of 32k): everything after the LAST layer's attention is row-wise -- o + residual,
@@ -620,16 +680,16 @@ class LlamaModel:
         pg = self.proj_group
         R = self.STREAM_CFG_RES16
         (qw, qe), (ow, oe) = self._stream_w(L.qkv_w, "qkv", c), self._stream_w(L.o_w, "o", R)
-        qkv = ops.stream_gemm(h, qw, splits=s, cfg=c, nt=True, norm_eps=cfg.eps, w_group=pg.get("qkv", 1), w_exps=qe)
+        qkv = ops.stream_gemm(h, qw, splits=s, cfg=c, nt=True, norm_eps=cfg.eps, w_group=pg.get("qkv", 1), **qe)
         q = kv.write(li, qkv, meta.positions, self.cos_sin, meta.slots, self.hq, self.hkv, D)
         a = kv.decode_attention(li, q, meta.block_tables, meta.ctx_lens, meta.part_size, meta.workspace,
                                 order=meta.order)
-        h1 = ops.stream_gemm(a.view(T, self.hq * D), ow, residual=h, cfg=R, nt=True, w_group=pg.get("o", 1), w_exps=oe)
+        h1 = ops.stream_gemm(a.view(T, self.hq * D), ow, residual=h, cfg=R, nt=True, w_group=pg.get("o", 1), **oe)
         gc, _ = self._stream_choice("gate_up", T, L.gate_up_w.shape[0], L.gate_up_w.shape[1])
         (gw, ge), (dw, de) = self._stream_w(L.gate_up_w, "gate_up", gc), self._stream_w(L.down_w, "down", R)
         act = ops.stream_gemm(h1, gw, epilogue=ops.EPI_SWIGLU8, cfg=gc, nt=True, norm_eps=cfg.eps,
-                              w_group=pg.get("gate_up", 1), w_exps=ge)
-        return ops.stream_gemm(act, dw, residual=h1, cfg=R, nt=True, w_group=pg.get("down", 1), w_exps=de)
+                              w_group=pg.get("gate_up", 1), **ge)
+        return ops.stream_gemm(act, dw, residual=h1, cfg=R, nt=True, w_group=pg.get("down", 1), **de)
 
     # Small decode batches: the paged attention is a chain of dependent memory round trips on a few
     # dozen CUs (~15 us per layer at batch 1 while HBM idles).  ``l3_warm_mb`` > 0 appends
@@ -644,7 +704,7 @@ class LlamaModel:
         if not self.l3_warm_mb or T > self.L3_WARM_MAX_M or not ref.is_cuda:
             return None
         o_w, gu_w = L.o_w, L.gate_up_w
-        if isinstance(o_w, Fp8Proj):  # the bytes the decode GEMM streams
+        if isinstance(o_w, (Fp8Proj, Mxfp4Proj)):  # the bytes the decode GEMM streams
             o_w, gu_w = o_w.data, gu_w.data
         budget = int(self.l3_warm_mb * 2 ** 20) & ~15
         ob = o_w.numel() * o_w.element_size()

@@ -998,6 +998,52 @@ def shuffle_rows_into_fp8(dst: torch.Tensor, rows: torch.Tensor, data: torch.Ten
     v6[rows // 16, :, :, rows % 16, :, :] = data.to(dst.device).reshape(-1, K // 64, 2, 4, 8).permute(0, 1, 3, 2, 4)
 
 
+weight_quantize_mxfp4 = ref.weight_quantize_mxfp4
+weight_dequantize_mxfp4 = ref.weight_dequantize_mxfp4
+
+
+def shuffle_weights_mxfp4(codes: torch.Tensor, group: int = 1) -> torch.Tensor:
+    """e2m1 codes [N, K/2] (uint8, two per byte, row-major: ``weight_quantize_mxfp4``) -> the MXFP4
+    fragment layout [N/16][K/128][64 lanes][16 B] the streaming decode GEMM's MXFP4 arm reads: lane l
+    holds row l & 15, its bytes 4c .. 4c + 3 are the 8 codes of k = 128j + 32c + 8 (l >> 4) .. + 8 -- the
+    lane's operand of the c-th 32-deep MFMA chunk, and exactly one MX block of the row per chunk -- so
+    one 16-byte lane load (a fully coalesced 1 KB wave read) feeds four chunks.  ``group`` G > 1 as in
+    ``shuffle_weights``: the fragments of G consecutive 16-row blocks adjacent per 128-deep k step.
+    Returned with shape [N, K/2]."""
+    expect(codes.dtype == torch.uint8 and codes.dim() == 2, "shuffle_weights_mxfp4 takes e2m1 code bytes (uint8 [N, K/2])")
+    N, K = codes.shape[0], codes.shape[1] * 2
+    expect(N % (16 * group) == 0 and K % 128 == 0, "shuffle_weights_mxfp4 needs N % (16 group) == 0 and K % 128 == 0")
+    f = codes.reshape(N // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5)  # [blk, j, l >> 4, l & 15, c, 4 B]
+    if group > 1:
+        f = f.reshape(N // (16 * group), group, K // 128, 1024).permute(0, 2, 1, 3)
+    return f.contiguous().view(N, K // 2)
+
+
+def unshuffle_weights_mxfp4(codes: torch.Tensor, group: int = 1) -> torch.Tensor:
+    """Inverse of ``shuffle_weights_mxfp4``."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if group > 1:
+        codes = codes.reshape(N // (16 * group), K // 128, group, 1024).permute(0, 2, 1, 3)
+    return codes.reshape(N // 16, K // 128, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).contiguous().view(N, K // 2)
+
+
+def shuffle_scales_mxfp4(scales: torch.Tensor) -> torch.Tensor:
+    """MXFP4 scale bytes [N, K/32] (uint8, row-major) -> [N/16][K/128][16 rows][4 B]: the four scale
+    bytes of row l & 15 for one 128-deep fragment are one aligned dword, which lane l of the wave
+    that owns the 16-row block loads next to the fragment's codes (64 bytes per fragment, each read
+    once per launch).  The same for every ``group`` of the codes.  Returned with shape [N, K/32]."""
+    expect(scales.dtype == torch.uint8 and scales.dim() == 2, "shuffle_scales_mxfp4 takes scale bytes (uint8 [N, K/32])")
+    N, KB = scales.shape
+    expect(N % 16 == 0 and KB % 4 == 0, "shuffle_scales_mxfp4 needs N % 16 == 0 and K % 128 == 0")
+    return scales.reshape(N // 16, 16, KB // 4, 4).permute(0, 2, 1, 3).contiguous().view(N, KB)
+
+
+def unshuffle_scales_mxfp4(scales: torch.Tensor) -> torch.Tensor:
+    """Inverse of ``shuffle_scales_mxfp4``."""
+    N, KB = scales.shape
+    return scales.reshape(N // 16, KB // 4, 16, 4).permute(0, 2, 1, 3).contiguous().view(N, KB)
+
+
 def fp8_scan_max_m(K: int) -> int:
     """Most queries one ``score_candidates_fp8`` launch takes at width K (the scan's LDS budget)."""
     return 96 if K <= 768 else 64
@@ -1073,7 +1119,7 @@ def index_dequant_blocks(data_shuf, exps, b0: int, b1: int, out, out_block: int 
 
 
 def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=False, cfg=0, norm_eps: float = 0.0,
-                slab_dtype=torch.float32, w_group: int = 1, w_exps=None):
+                slab_dtype=torch.float32, w_group: int = 1, w_exps=None, w_scales=None):
     """Decode GEMM y = x w^T on the warp-specialised streaming kernel (``stream_gemm.hip``): bf16
     [M, N] (optional residual add), SwiGLU [M, N/2] over 16- / 8-row interleaved [gate | up] rows, or
     fp32 K-slice slabs [S, M, N] (their sum is the product; consumers sum them in their prologue or
@@ -1088,11 +1134,21 @@ def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=F
     ``w_exps`` (FP8 weights, W8A16): ``w`` is the uint8 ``shuffle_weights_fp8`` copy of the e4m3fn
     bytes and ``w_exps`` [N] the rows' exponent bytes (``weight_quantize_fp8``); the result is, bit
     for bit, what the bf16 kernel gives on ``shuffle_weights(weight_dequantize_fp8(...))``.  Only
-    the configurations with ``native().stream_gemm_fp8_ok(cfg)``; K % 64 == 0."""
-    fp8 = w_exps is not None
+    the configurations with ``native().stream_gemm_fp8_ok(cfg)``; K % 64 == 0.
+
+    ``w_scales`` (MXFP4 weights, W4A16; not together with ``w_exps``): ``w`` is the uint8
+    ``shuffle_weights_mxfp4`` copy [N, K/2] of the e2m1 codes and ``w_scales`` the
+    ``shuffle_scales_mxfp4`` copy [N, K/32] of the block scale bytes (``weight_quantize_mxfp4``); the
+    result is, bit for bit, what the bf16 kernel gives on
+    ``shuffle_weights(weight_dequantize_mxfp4(...))``.  Only the configurations with
+    ``native().stream_gemm_mxfp4_ok(cfg)``; K % 128 == 0.  On the CPU both are row-major."""
+    fp8, fp4 = w_exps is not None, w_scales is not None
+    expect(not (fp8 and fp4), "w_exps (FP8 weights) and w_scales (MXFP4 weights) are mutually exclusive")
     if not x.is_cuda:
         if fp8:
             w = weight_dequantize_fp8(w, w_exps).to(x.dtype)
+        if fp4:
+            w = weight_dequantize_mxfp4(w, w_scales).to(x.dtype)
         y = _ref_stream_gemm(x, w, splits=splits, epilogue=epilogue, residual=residual, norm_eps=norm_eps)
         return y.to(slab_dtype) if splits > 1 else y
     expect(norm_eps <= 0 or residual is None, "the consumer RMSNorm takes no residual add")
@@ -1103,6 +1159,16 @@ def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=F
         expect(w_exps.dtype == torch.uint8 and w_exps.is_cuda and w_exps.dim() == 1 and w_exps.shape[0] == w.shape[0]
                and w_exps.is_contiguous() and w_exps.data_ptr() % 4 == 0,
                "w_exps must be the uint8 [N] row exponents (contiguous, 4-byte aligned)")
+    elif fp4:
+        expect(x.dtype == torch.bfloat16 and w.dtype == torch.uint8 and w.is_cuda and w.dim() == 2 and w.is_contiguous()
+               and w.data_ptr() % 16 == 0, "MXFP4 weights: bf16 x, contiguous 16-byte aligned uint8 fragment copy [N, K/2]")
+        expect(native().stream_gemm_mxfp4_ok(cfg), f"stream_gemm cfg {cfg} has no MXFP4-weight instantiation")
+        expect(w.shape[1] % 64 == 0, "MXFP4 weights need K % 128 == 0")
+        expect(w_scales.dtype == torch.uint8 and w_scales.is_cuda and w_scales.dim() == 2
+               and tuple(w_scales.shape) == (w.shape[0], w.shape[1] // 16) and w_scales.is_contiguous()
+               and w_scales.data_ptr() % 4 == 0,
+               "w_scales must be the uint8 [N, K/32] shuffle_scales_mxfp4 copy (contiguous, 4-byte aligned)")
+        same_device(x, w, w_scales)
     else:
         expect(x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16, "bf16 operands required")
     expect(x.stride(-1) == 1 and w.stride(-1) == 1, "operands must be K-contiguous")
@@ -1110,7 +1176,7 @@ def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=F
     N = w.shape[0]
     bn = native().stream_gemm_bn(cfg)
     expect(bn > 0 and M <= native().stream_gemm_max_m(cfg), f"stream_gemm cfg {cfg}: bad config or M too large")
-    expect(w.shape[1] == K and N % bn == 0 and K % (splits * STREAM_KS) == 0,
+    expect(w.shape[1] * (2 if fp4 else 1) == K and N % bn == 0 and K % (splits * STREAM_KS) == 0,
            f"stream_gemm needs N % {bn} == 0 and K % ({STREAM_KS}*splits) == 0")
     expect(x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0, "row strides must be multiples of 8")
     if native().stream_gemm_shuffled(cfg):
@@ -1138,6 +1204,12 @@ def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=F
                                  residual.stride(0) if residual is not None else 0, M, N, K, splits, int(epilogue),
                                  stream(x), int(bool(nt)), int(cfg), float(norm_eps),
                                  int(splits > 1 and out.dtype == torch.bfloat16), int(w_group))
+        return out
+    if fp4:
+        native().stream_gemm_mxfp4(ptr(x), x.stride(0), ptr(w), ptr(w_scales), ptr(out), ldo, ptr(residual),
+                                   residual.stride(0) if residual is not None else 0, M, N, K, splits, int(epilogue),
+                                   stream(x), int(bool(nt)), int(cfg), float(norm_eps),
+                                   int(splits > 1 and out.dtype == torch.bfloat16), int(w_group))
         return out
     native().stream_gemm(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(out), ldo, ptr(residual),
                          residual.stride(0) if residual is not None else 0, M, N, K, splits, int(epilogue), stream(x),

@@ -206,6 +206,55 @@ def weight_dequantize_fp8(data, exps):
     return kv_dequantize(data, exps).to(torch.bfloat16)
 
 
+MXFP4_BLOCK = 32  # k per E8M0 scale byte (OCP MX)
+# magnitudes of the e2m1 codes 0..7 (bit 3 of a code is the sign)
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def weight_quantize_mxfp4(w):
+    """Projection weights [N, K] (K % 32 == 0) -> (e2m1 codes uint8 [N, K/2], scale bytes uint8 [N, K/32]):
+    OCP MXFP4 along K, one E8M0 byte b (scale 2^(b - 127)) per block of 32 consecutive k of a row.
+
+    The scale is the smallest power of two 2^e with amax / 2^e <= 6 (nothing clips), found with
+    integer operations on the bits of the block's amax, as ``kv_quantize`` does: with amax =
+    1.M x 2^(E - 127) it is b = E - 2, or E - 1 when 1.M > 1.5.  b is clamped to [2, 252], so every
+    dequantised value is a finite normal bf16 (amax beyond 6 x 2^125 then clips to 6); a zero block has
+    b = 127 and zero codes.  Codes: x / 2^(b - 127) (exact) rounded to the grid 0, 0.5, 1, 1.5, 2, 3, 4, 6
+    with ties to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4);
+    a zero is code 0, never -0.  Byte i of a row holds k = 2i in its low nibble and k = 2i + 1 in its
+    high one (the order in which v_cvt_scalef32_pk_bf16_fp4 delivers them)."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError("weight_quantize_mxfp4 needs K % 32 == 0")
+    xf = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = xf.abs().amax(-1)
+    bits = amax.contiguous().view(torch.int32)
+    E, M = (bits >> 23) & 0xFF, bits & 0x7FFFFF
+    b = (E - 2 + (M > 0x400000).to(torch.int32)).clamp(2, 252)
+    b = torch.where(amax == 0, torch.full_like(b, 127), b)
+    inv = ((254 - b) << 23).view(torch.float32)  # 2^-(b - 127)
+    y = xf * inv[..., None]
+    a = y.abs().clamp(max=MXFP4_GRID[-1])
+    code = torch.zeros(a.shape, dtype=torch.int32, device=a.device)
+    for i in range(7):  # the midpoint between codes i and i + 1 goes to the even one
+        mid = (MXFP4_GRID[i] + MXFP4_GRID[i + 1]) / 2
+        code += (a > mid if i % 2 == 0 else a >= mid).to(torch.int32)
+    code |= ((y < 0) & (code > 0)).to(torch.int32) << 3
+    code = code.reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8), b.to(torch.uint8)
+
+
+def weight_dequantize_mxfp4(codes, scales):
+    """(codes [N, K/2], scale bytes [N, K/32]) -> bf16 [N, K]; exact (a code's magnitude has at most two
+    significant bits and the scale bytes of ``weight_quantize_mxfp4`` keep every product normal)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    lut = torch.tensor(MXFP4_GRID + tuple(-v for v in MXFP4_GRID), dtype=torch.float32, device=codes.device)
+    c = codes.to(torch.int64)
+    vals = lut[torch.stack([c & 15, c >> 4], -1).reshape(N, K)]
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (vals.reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * scale[..., None]).reshape(N, K).to(torch.bfloat16)
+
+
 def rope_kv_write_fp8(qkv, positions, cos_sin, k_data, k_exp, v_data, v_exp, slots, Hq, Hkv, D, block_size):
     """``rope_kv_write`` into an FP8 cache: what the bf16 cache would hold is quantised per row."""
     T = qkv.shape[0]

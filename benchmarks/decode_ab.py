@@ -112,7 +112,16 @@ ARMS = {
     "wmx": {"_w": "mxfp4"},
     "wmx_deep": {"_w": "mxfp4", "_ring": 1},
     "wmx_off": {"_w": "mxfp4", "_stream_off": True},  # the MXFP4 model streaming its bf16 copies
+    # MXFP4 as the only copy (mxfp4_weights_only: a model of its own): calls without an MXFP4 arm read the
+    # dequantiser's scratch image (gate_up on gemm_mid at batches 129..256); "_stream_off": every call does
+    "wmx_only": {"_w": "mxfp4", "_only": True},
+    "wmx_only_off": {"_w": "mxfp4", "_only": True, "_stream_off": True},
 }
+
+
+def weights_key(spec: dict):
+    """The model an arm runs on: its weight dtype, "+only" for the one-copy MXFP4 model (None: the first)."""
+    return (spec["_w"] + ("+only" if spec.get("_only") else "")) if spec.get("_w") else None
 
 
 def tuned_model_class():
@@ -144,20 +153,23 @@ def main():
     from django_assistant_bot_amd.engine.llm_engine import LLMEngine, SamplingParams
 
     torch.manual_seed(0)
-    wds = []  # the weight dtypes the arms ask for, in order: one model (and engine) each
+    wds = []  # the weights the arms ask for (``weights_key``), in order: one model (and engine) each
     for a in args.arms.split(","):
-        if ARMS[a].get("_w") and ARMS[a]["_w"] not in wds:
-            wds.append(ARMS[a]["_w"])
+        if weights_key(ARMS[a]) and weights_key(ARMS[a]) not in wds:
+            wds.append(weights_key(ARMS[a]))
     primary = wds[0] if wds else "bf16"
-    kv_gb = 120 if len(wds) <= 1 else 60
-    eng = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=kv_gb, max_prefill_tokens=32768,
-                    block_size=args.block_size, weight_dtype=primary)
-    eng.model.__class__ = tuned_model_class()  # same object, overridable stream choice
+    kv_gb = 120 if len(wds) <= 1 else 60 if len(wds) == 2 else 40
+
+    def build(wd):
+        e = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=kv_gb, max_prefill_tokens=32768,
+                      block_size=args.block_size, weight_dtype=wd.split("+")[0], mxfp4_weights_only=wd.endswith("+only"))
+        e.model.__class__ = tuned_model_class()  # same object, overridable stream choice
+        return e
+
+    eng = build(primary)
     engs = {primary: eng}
     for wd in wds[1:]:
-        engs[wd] = LLMEngine("llama-3-8b", device="cuda", max_batch=args.batch, kv_cache_gb=kv_gb,
-                             max_prefill_tokens=32768, block_size=args.block_size, weight_dtype=wd)
-        engs[wd].model.__class__ = tuned_model_class()
+        engs[wd] = build(wd)
     g = torch.Generator().manual_seed(1)
     sp = SamplingParams(max_new_tokens=6000, ignore_eos=True)
     prompts = [torch.randint(0, 128000, (args.prompt + int(torch.randint(-100, 100, (1,), generator=g)),),
@@ -190,8 +202,8 @@ def main():
         for a in arms:
             spec = dict(ARMS[a])
             # (restart() and the steps below follow it; the FP8-KV engine shares the first model)
-            eng = eng8 if spec.get("_kv") == "fp8" else engs.get(spec.get("_w"), eng16)
-            assert eng.model.weight_dtype == spec.get("_w", primary), "this arm's weights are not this engine's"
+            eng = eng8 if spec.get("_kv") == "fp8" else engs.get(weights_key(spec), eng16)
+            assert eng.model.weight_dtype == spec.get("_w", primary.split("+")[0]), "this arm's weights are not this engine's"
             restart()
             eng.model.overrides = {k: v for k, v in spec.items() if not k.startswith("_")}
             eng.long_part_size = spec.get("_part", base_part)

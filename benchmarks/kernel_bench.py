@@ -252,6 +252,62 @@ def stream_mxfp4_sweep(Ms=(1, 16, 64, 128, 256), rounds=3):
             del w16, w8, w4
 
 
+def dequant_mxfp4_sweep(rounds=3, pair_m=192):
+    """``ops.weight_dequant_mxfp4`` (the one-copy MXFP4 model's in-launch dequantiser) on the four
+    Llama-3-8B projection shapes, cold codes (distinct copies beyond the Infinity Cache) into ONE scratch
+    as in the model, with default (``st``) and non-temporal (``nt``) stores of the image, alternating
+    round by round.  GB/s counts the bytes read and written (codes + scales + bf16 image).  ``pair_*``:
+    the dequantiser followed by the MFMA GEMM that reads the scratch at M = ``pair_m`` (what the store
+    policy is for), and ``gemm_us`` that GEMM alone on a resident bf16 copy."""
+    from django_assistant_bot_amd.models.llama import LlamaModel
+
+    nat = ops.native()
+    shapes = (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    nt0 = nat.weight_dequant_mxfp4_nt()
+    for name, N, K in shapes:
+        grp = LlamaModel.PROJ_GROUPS.get(name, 1)
+        epi = ops.EPI_SWIGLU8 if name == "gate_up" else ops.EPI_NONE
+        mxb = N * K // 2 + N * K // 32
+        ncopy = max(2, int(6e8 // mxb) + 1)
+        w4 = []
+        for _ in range(ncopy):
+            codes = torch.randint(0, 256, (N, K // 2), dtype=torch.uint8, device="cuda")
+            scales = torch.randint(118, 130, (N, K // 32), dtype=torch.uint8, device="cuda")
+            w4.append((codes, scales))  # (any bytes are a valid fragment copy)
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device="cuda")
+        a = torch.randn(pair_m, K, device="cuda").to(torch.bfloat16)
+        resident = ops.weight_dequant_mxfp4(*w4[0], torch.empty(N * K, dtype=torch.bfloat16, device="cuda"), grp)
+
+        def gemm(w):
+            return ops.gemm_bt(a, w, epilogue=epi, shuffled=True, b_group=grp)
+
+        def run(nt, pair):
+            nat.weight_dequant_mxfp4_set_nt(nt)  # (read at launch: baked into the captured graph)
+            calls = []
+            for c, s in w4:
+                calls.append(lambda c=c, s=s: ops.weight_dequant_mxfp4(c, s, scratch, grp))
+                if pair:
+                    calls.append(lambda: gemm(scratch[:N * K].view(N, K)))
+            return graph_time(calls) * (2 if pair else 1)
+
+        arms = {"st": lambda: run(0, False), "nt": lambda: run(1, False), "pair_st": lambda: run(0, True),
+                "pair_nt": lambda: run(1, True), "gemm": lambda: graph_time([lambda: gemm(resident)] * 4)}
+        times = {k: [] for k in arms}
+        for _ in range(rounds):
+            for k, fn in arms.items():
+                times[k].append(fn())
+        nat.weight_dequant_mxfp4_set_nt(nt0)
+        res = {"op": f"dequant-mxfp4-{name}", "N": N, "K": K, "group": grp, "pair_m": pair_m, "copies": ncopy}
+        for k in arms:
+            t = sorted(times[k])[len(times[k]) // 2]
+            res[f"{k}_us"] = round(t * 1e6, 1)
+            res[f"{k}_us_min_max"] = [round(min(times[k]) * 1e6, 1), round(max(times[k]) * 1e6, 1)]
+            if k in ("st", "nt"):
+                res[f"{k}_gbps"] = round((mxb + 2 * N * K) / t / 1e9, 1)
+        emit(**res)
+        del w4, scratch, resident
+
+
 def attn_suite():
     # prefill: 16 sequences x 1024 tokens, Llama-3-8B heads
     B, T, Hq, Hkv, D, bs = 16, 1024, 32, 8, 128, 64
@@ -524,6 +580,8 @@ if __name__ == "__main__":
         stream_fp8_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (1, 16, 64, 128, 256))
     if which == "stream_mxfp4":
         stream_mxfp4_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (1, 16, 64, 128, 256))
+    if which == "dequant_mxfp4":
+        dequant_mxfp4_sweep()
     if which == "decode":
         decode_sweep()
     if which in ("decode", "decodefp8"):

@@ -327,6 +327,13 @@ PYBIND11_MODULE(_native, m) {
   m.def("stream_gemm_mxfp4_nwin", &dab::stream_gemm_mxfp4_nwin);
   m.def("stream_gemm_mxfp4_set_deep", &dab::stream_gemm_mxfp4_set_deep);
   m.def("stream_gemm_mxfp4_deep", &dab::stream_gemm_mxfp4_deep);
+  m.def("weight_dequant_mxfp4", [](u codes, u scales, u out, long N, long K, int group, int grid_cap, u s) {
+    check(dab::weight_dequant_mxfp4(CVP(codes), CVP(scales), VP(out), N, K, group, grid_cap, ST(s)),
+          "weight_dequant_mxfp4");
+  }, py::arg("codes"), py::arg("scales"), py::arg("out"), py::arg("N"), py::arg("K"), py::arg("group"),
+     py::arg("grid_cap"), py::arg("s"));
+  m.def("weight_dequant_mxfp4_set_nt", &dab::weight_dequant_mxfp4_set_nt);
+  m.def("weight_dequant_mxfp4_nt", &dab::weight_dequant_mxfp4_nt);
   m.def("stream_gemm_bn", &dab::stream_gemm_bn);
   m.def("stream_gemm_max_m", &dab::stream_gemm_max_m);
   m.def("stream_gemm_set_slice_xcd", &dab::stream_gemm_set_slice_xcd);

@@ -147,6 +147,16 @@ int stream_gemm_mxfp4_nwin(int cfg);  // weight-ring stages of cfg's MXFP4 arm a
 // MXFP4 arm ring depth: 0 = the bf16 configuration's stages, 1 = twice that; A/B switch
 void stream_gemm_mxfp4_set_deep(int on);
 int stream_gemm_mxfp4_deep();
+// weight_dequant.hip: MXFP4 codes (ops.shuffle_weights_mxfp4(…, group), 16-byte aligned) and scales
+// (ops.shuffle_scales_mxfp4, 4-byte aligned) -> the bf16 ops.shuffle_weights(…, group) image of the
+// dequantised [N, K] weights, written to the first N K elements of `out` (16-byte aligned; may be larger).
+// Exact.  grid_cap > 0 bounds the workgroups (0: the default).  K % 128, N % (16 group), a null or
+// misaligned pointer, or N K 2 >= 2^31 bytes with group > 1 -> hipErrorInvalidValue, nothing launched
+int weight_dequant_mxfp4(const void* codes, const void* scales, void* out, long N, long K, int group, int grid_cap,
+                         hipStream_t s);
+// store policy of that image: 0 = default, 1 = non-temporal; A/B switch
+void weight_dequant_mxfp4_set_nt(int on);
+int weight_dequant_mxfp4_nt();
 // fp32 (or bf16: slab_bf16) split-K slabs [S][M][N] -> bf16 [M, N] (+ residual)
 int slab_reduce(void* out, long ldo, const void* slabs, int S, int M, int N, const void* residual, long ldr,
                 hipStream_t s, int slab_bf16 = 0);

@@ -113,7 +113,8 @@ class LLMEngine:
                  part_size: int = 512, kv_memory_fraction: float = 0.85, mixed_prefill_tokens: int = 0,
                  pipeline_decode: bool = True, shared_model: LlamaModel | None = None,
                  kv_cache_dtype: str | None = None, kv_scratch_blocks: int | None = None,
-                 weight_dtype: str | None = None, fp8_weights_only: bool | None = None):
+                 weight_dtype: str | None = None, fp8_weights_only: bool | None = None,
+                 mxfp4_weights_only: bool | None = None):
         """``shared_model``: serve with another engine's ``LlamaModel`` (one copy of the weights, a
         KV pool / scheduler / HIP graphs of this engine's own; e.g. two engines on two streams whose
         prefill and decode phases overlap: bench.py --mode overlap).
@@ -135,7 +136,14 @@ class LLMEngine:
         memory goes to KV blocks); ``None`` reads ``DAB_WEIGHT_FP8_ONLY`` (1 / true / yes / on) from the
         environment, else off.  Refused (ValueError) without ``weight_dtype="fp8"``, under TP and on
         the GPU for projections gemm256 does not take; with ``shared_model`` the engine adopts the
-        model's."""
+        model's.
+
+        ``mxfp4_weights_only`` (opt-in on top of ``weight_dtype="mxfp4"``, TP 1, not with
+        ``fp8_weights_only``): the MXFP4 codes and scales are the only copy of every projection
+        (``LlamaModel(mxfp4_weights_only=True)``: 4.25 / 16 of the bf16 projection memory plus one scratch
+        per stream, ``stats["weight_scratch_bytes"]``; bit-identical to the two-copy MXFP4 model); ``None``
+        reads ``DAB_WEIGHT_MXFP4_ONLY`` from the environment, else off.  The same refusals as the model's;
+        with ``shared_model`` the engine adopts the model's."""
         self.cfg = decoder_config(model) if isinstance(model, str) else model
         cfg = self.cfg
         if shared_model is not None:
@@ -147,11 +155,19 @@ class LLMEngine:
             if fp8_weights_only is not None and bool(fp8_weights_only) != have_only:
                 raise ValueError(f"fp8_weights_only={fp8_weights_only!r} conflicts with the shared model's {have_only!r}")
             fp8_weights_only = have_only
+            have_only = bool(getattr(shared_model, "mxfp4_weights_only", False))
+            if mxfp4_weights_only is not None and bool(mxfp4_weights_only) != have_only:
+                raise ValueError(f"mxfp4_weights_only={mxfp4_weights_only!r} conflicts with the shared model's "
+                                 f"{have_only!r}")
+            mxfp4_weights_only = have_only
         elif weight_dtype is None:
             weight_dtype = os.environ.get("DAB_WEIGHT_DTYPE") or "bf16"
         if fp8_weights_only is None:
             fp8_weights_only = parse_flag(os.environ.get("DAB_WEIGHT_FP8_ONLY"))
         fp8_weights_only = bool(fp8_weights_only)
+        if mxfp4_weights_only is None:
+            mxfp4_weights_only = parse_flag(os.environ.get("DAB_WEIGHT_MXFP4_ONLY"))
+        mxfp4_weights_only = bool(mxfp4_weights_only)
         if weight_dtype not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
         if weight_dtype != "bf16" and tp_size > 1:
@@ -160,8 +176,13 @@ class LLMEngine:
             raise ValueError("fp8_weights_only needs weight_dtype='fp8'")
         if fp8_weights_only and tp_size > 1:
             raise ValueError("fp8_weights_only does not support tensor parallelism (tp_size > 1)")
+        if mxfp4_weights_only and fp8_weights_only:
+            raise ValueError("mxfp4_weights_only and fp8_weights_only are mutually exclusive")
+        if mxfp4_weights_only and weight_dtype != "mxfp4":
+            raise ValueError("mxfp4_weights_only needs weight_dtype='mxfp4'")
         self.weight_dtype = weight_dtype
         self.fp8_weights_only = fp8_weights_only
+        self.mxfp4_weights_only = mxfp4_weights_only
         if kv_cache_dtype is None:
             kv_cache_dtype = os.environ.get("DAB_KV_CACHE_DTYPE") or "bf16"
         if kv_cache_dtype not in ("bf16", "fp8"):
@@ -195,7 +216,8 @@ class LLMEngine:
         else:
             self.model = LlamaModel(cfg, weights, self.device, tp_group=tp_group, tp_size=tp_size,
                                     interleaved_mlp=interleaved_mlp, consume=own_weights, tp_rank=tp_rank,
-                                    weight_dtype=weight_dtype, fp8_weights_only=fp8_weights_only)
+                                    weight_dtype=weight_dtype, fp8_weights_only=fp8_weights_only,
+                                    mxfp4_weights_only=mxfp4_weights_only)
         del weights
         if self.is_gpu and shared_model is None:
             # the caller's weight dict held the row-major originals while the model converted them
@@ -234,6 +256,9 @@ class LLMEngine:
             elif self.is_gpu:
                 free, _ = torch.cuda.mem_get_info(self.device)
                 free -= KVCache.scratch_bytes(scratch, hkv, block_size, cfg.head_dim)
+                # ``mxfp4_weights_only``: the weight scratches of this engine's capture stream and of a
+                # caller's side stream are allocated on first use, after the pool
+                free -= 2 * self.model.mxfp4_scratch_bytes()
                 num_blocks = int(free * kv_memory_fraction // per_block)
             else:
                 num_blocks = 4 * self.max_blocks_per_seq
@@ -256,10 +281,12 @@ class LLMEngine:
                       # the projection weights the decode GEMM streams (8: ``weight_dtype="fp8"``, 4:
                       # ``"mxfp4"``, e2m1 codes; their block scales add a quarter of a bit)
                       "weight_bits": {"fp8": 8, "mxfp4": 4}.get(weight_dtype, 16),
-                      # whether the projections keep a bf16 copy (False: ``fp8_weights_only``), and the
-                      # projection bytes resident, counted from the model's tensors
-                      "weight_bf16_copy": not fp8_weights_only,
-                      "weight_bytes": self.model.projection_bytes()}
+                      # whether the projections keep a bf16 copy (False: ``fp8_weights_only`` /
+                      # ``mxfp4_weights_only``), the projection bytes resident, counted from the model's
+                      # tensors, and one bf16 image scratch of ``mxfp4_weights_only`` (0 without it)
+                      "weight_bf16_copy": not (fp8_weights_only or mxfp4_weights_only),
+                      "weight_bytes": self.model.projection_bytes(),
+                      "weight_scratch_bytes": self.model.mxfp4_scratch_bytes()}
         # decode static buffers (graph inputs / outputs)
         self.use_graphs = use_graphs and self.is_gpu
         dev = self.device
@@ -316,6 +343,7 @@ class LLMEngine:
         self._graphs: dict = {}
         self._buckets = _bucket_sizes(max_batch)
         self._graph_pool = None
+        self._capture_stream = None
         # GPU spans of the engine phases (HIP events, read where the host syncs anyway) -> stats
         self.timer = trace.GpuTimer(enabled=self.is_gpu)
         # test hook: called at the start of every step (fault injection, e.g. raise a HIP error)
@@ -1123,7 +1151,11 @@ class LLMEngine:
 
     def _capture(self, Bp: int):
         try:
-            s = torch.cuda.Stream(self.device)
+            # one capture stream per engine: a per-stream resource the warm-up allocates (the model's
+            # ``mxfp4_weights_only`` weight scratch) exists once, and this engine's graphs alone point at it
+            if self._capture_stream is None:
+                self._capture_stream = torch.cuda.Stream(self.device)
+            s = self._capture_stream
             s.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(s):
                 self._decode_body(Bp)  # warm-up (allocator, lazy init) outside the graph

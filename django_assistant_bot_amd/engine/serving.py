@@ -231,11 +231,13 @@ def get_llm_worker(model: str, **engine_kwargs) -> LLMWorker:
             engine_kwargs.setdefault("max_prefill_tokens", setting("MAX_BATCH_TOKENS", 65536))
             engine_kwargs.setdefault("kv_cache_dtype", setting("KV_CACHE_DTYPE", None))  # None: env, else bf16
             engine_kwargs.setdefault("weight_dtype", setting("WEIGHT_DTYPE", None))  # (likewise)
-            if "fp8_weights_only" not in engine_kwargs:  # None: DAB_WEIGHT_FP8_ONLY, else off
-                from .llm_engine import parse_flag
+            # None: DAB_WEIGHT_FP8_ONLY / DAB_WEIGHT_MXFP4_ONLY, else off
+            for kw, name in (("fp8_weights_only", "WEIGHT_FP8_ONLY"), ("mxfp4_weights_only", "WEIGHT_MXFP4_ONLY")):
+                if kw not in engine_kwargs:
+                    from .llm_engine import parse_flag
 
-                only = setting("WEIGHT_FP8_ONLY", None)
-                engine_kwargs["fp8_weights_only"] = None if only is None else parse_flag(only)
+                    only = setting(name, None)
+                    engine_kwargs[kw] = None if only is None else parse_flag(only)
             if engine_kwargs["device"] == "cpu":
                 engine_kwargs.setdefault("max_model_len", 2048)
             w = _llm[key] = LLMWorker(LLMEngine(model, **engine_kwargs))

@@ -84,30 +84,36 @@ class Mxfp4Proj:
     row in the ``ops.shuffle_scales_mxfp4`` layout, streamed by the decode GEMM (stream_gemm's MXFP4
     arm), and ``w``, a bf16 ``ops.shuffle_weights`` copy of the DEQUANTISED values for the MFMA GEMMs
     and every stream_gemm configuration without an MXFP4 arm.  Both hold the same numbers.
-    ``group``: the row-block group of the codes and of the bf16 copy (the scales have one layout)."""
+    ``group``: the row-block group of the codes and of the bf16 copy (the scales have one layout).
+
+    ``mxfp4_weights_only``: ``w`` is None and the codes and scales are the ONLY copy; a call without an
+    MXFP4 arm reads a bf16 image that ``ops.weight_dequant_mxfp4`` writes into the model's scratch right
+    before it (``LlamaModel._bf16_w``): the same bytes ``w`` would hold."""
 
     __slots__ = ("w", "data", "scales", "group")
 
-    def __init__(self, w: torch.Tensor, data: torch.Tensor, scales: torch.Tensor, group: int = 1):
+    def __init__(self, w: torch.Tensor | None, data: torch.Tensor, scales: torch.Tensor, group: int = 1):
         self.w, self.data, self.scales, self.group = w, data, scales, group
 
     @classmethod
-    def from_rows(cls, codes: torch.Tensor, scales: torch.Tensor, group: int = 1) -> "Mxfp4Proj":
+    def from_rows(cls, codes: torch.Tensor, scales: torch.Tensor, group: int = 1,
+                  bf16_copy: bool = True) -> "Mxfp4Proj":
         """From row-major codes [N, K/2] and scale bytes [N, K/32] (``ops.weight_quantize_mxfp4``)."""
-        w = ops.shuffle_weights(ops.weight_dequantize_mxfp4(codes, scales), group)
+        w = ops.shuffle_weights(ops.weight_dequantize_mxfp4(codes, scales), group) if bf16_copy else None
         return cls(w, ops.shuffle_weights_mxfp4(codes, group), ops.shuffle_scales_mxfp4(scales), group)
 
     @property
     def shape(self):
-        return self.w.shape  # [N, K]
+        return torch.Size((self.data.shape[0], 2 * self.data.shape[1]))  # [N, K], as the bf16 copy's
 
     def nbytes(self) -> int:
         """Bytes resident for this projection, counted from its tensors."""
-        return sum(t.numel() * t.element_size() for t in (self.w, self.data, self.scales))
+        return sum(t.numel() * t.element_size() for t in (self.w, self.data, self.scales) if t is not None)
 
     def regroup(self, group: int) -> None:
         """Re-lay both copies for ``group``, in place (pointers stay valid)."""
-        self.w.copy_(ops.shuffle_weights(ops.unshuffle_weights(self.w, self.group), group))
+        if self.w is not None:
+            self.w.copy_(ops.shuffle_weights(ops.unshuffle_weights(self.w, self.group), group))
         self.data.copy_(ops.shuffle_weights_mxfp4(ops.unshuffle_weights_mxfp4(self.data, self.group), group))
         self.group = group
 
@@ -244,7 +250,7 @@ class LlamaModel:
     def __init__(self, cfg: DecoderConfig, weights: dict, device, tp_group=None, tp_size: int = 1,
                  interleaved_mlp: bool = False, fragment_layout: bool = True, consume: bool = False,
                  tp_rank: int | None = None, vocab_parallel: bool = True, small_norm_fused: bool | None = None,
-                 weight_dtype: str = "bf16", fp8_weights_only: bool = False):
+                 weight_dtype: str = "bf16", fp8_weights_only: bool = False, mxfp4_weights_only: bool = False):
         """``weight_dtype="fp8"`` (opt-in, TP 1): the qkv / o / gate_up / down weights are quantised at
         load time to e4m3fn bytes with one power-of-two exponent per output row
         (``ops.weight_quantize_fp8``) and the model computes with the dequantised values everywhere.
@@ -271,6 +277,16 @@ class LlamaModel:
         configuration has an MXFP4 arm, everything else reads a bf16 copy of the same values
         (1.27x the bf16 model's projection memory).  Otherwise the weights are the dequantised tensors.
 
+        ``mxfp4_weights_only`` (opt-in on top of ``weight_dtype="mxfp4"``, TP 1, fragment layout, not with
+        ``fp8_weights_only``): the codes and scales are the only copy of every projection (4.25 / 16 of
+        the bf16 model's projection memory).  Dispatch does not change: a streamed call whose
+        configuration has an MXFP4 arm reads the codes, every other call takes the kernel the two-copy
+        model takes, on a bf16 image that ``ops.weight_dequant_mxfp4`` writes right before it into one
+        scratch the size of the largest projection (``_bf16_w``; ``mxfp4_scratch_bytes``).  The image
+        holds the bytes the two-copy model keeps resident, so every step is bit-identical to that
+        model's.  Every projection must become an ``Mxfp4Proj`` on the GPU (K % 128 == 0, fragment
+        layout; ValueError otherwise).  On the CPU it changes nothing.
+
         ``consume``: the entries of ``weights`` are popped as the model takes them over, so each
         original is freed as soon as its fragment-layout copy exists (peak HBM = model + one
         tensor: 70B at TP 1 needs it, 2 x 140 GB would not fit in 288 GB).
@@ -294,6 +310,14 @@ class LlamaModel:
                 raise ValueError("fp8_weights_only needs the fragment layout (fragment_layout=True)")
             if not self.fp8_stream or self.FP8_STREAM_OFF:
                 raise ValueError("fp8_weights_only keeps no bf16 copy for fp8_stream=False / FP8_STREAM_OFF to stream")
+        self.mxfp4_weights_only = bool(mxfp4_weights_only)
+        if self.mxfp4_weights_only:
+            if self.fp8_weights_only:
+                raise ValueError("mxfp4_weights_only and fp8_weights_only are mutually exclusive")
+            if weight_dtype != "mxfp4":
+                raise ValueError("mxfp4_weights_only needs weight_dtype='mxfp4'")
+            if not fragment_layout:
+                raise ValueError("mxfp4_weights_only needs the fragment layout (fragment_layout=True)")
         self.cfg = cfg
         self.device = torch.device(device)
         if tp_rank is None:
@@ -328,6 +352,15 @@ class LlamaModel:
                 if N % 256 or K % 128:
                     raise ValueError(f"fp8_weights_only: {n} [{N}, {K}] needs N % 256 == 0 and K % 128 == 0 "
                                      "(the FP8 arm of gemm256 is its only MFMA kernel)")
+        if self.mxfp4_weights_only and self.device.type == "cuda":
+            if not self.frag:
+                raise ValueError("mxfp4_weights_only: the weights do not take the fragment layout")
+            for i in range(cfg.layers):
+                for n in ("qkv_w", "o_w", "gate_up_w", "down_w"):
+                    N, K = weights[f"l{i}.{n}"].shape
+                    if K % 128:
+                        raise ValueError(f"mxfp4_weights_only: l{i}.{n} [{N}, {K}] needs K % 128 == 0 (it would keep "
+                                         "no MXFP4 codes, only dequantised values)")
         take = weights.pop if consume else weights.__getitem__
 
         self.proj_group = {}
@@ -351,7 +384,8 @@ class LlamaModel:
             if fp8:
                 return Fp8Proj.from_rows(data, exps, self.proj_group[name], bf16_copy=not self.fp8_weights_only)
             if self.weight_dtype == "mxfp4" and codes is not None:
-                return Mxfp4Proj.from_rows(codes, scales, self.proj_group[name])
+                only = self.mxfp4_weights_only and self.device.type == "cuda"
+                return Mxfp4Proj.from_rows(codes, scales, self.proj_group[name], bf16_copy=not only)
             return ops.shuffle_weights(t, self.proj_group[name])
 
         def load(i, name, norm=None):
@@ -393,6 +427,15 @@ class LlamaModel:
             self.layers.append(DecoderLayer(an, qkv_w, load(i, "o"), mn, gu_w, load(i, "down")))
         if self.frag and consume:
             torch.cuda.empty_cache()
+        # ``mxfp4_weights_only``: the bf16 image scratch of ``_bf16_w``, one per stream, keyed by the
+        # stream's handle; the constructing stream's exists before the engine sizes the KV pool
+        self._mxfp4_scratch = {}
+        self._mxfp4_scratch_elems = 0
+        if self.mxfp4_weights_only and self.device.type == "cuda":
+            self._mxfp4_scratch_elems = max(w.shape[0] * w.shape[1] for L in self.layers
+                                            for w in (L.qkv_w, L.o_w, L.gate_up_w, L.down_w))
+            with torch.cuda.device(self.device):
+                self._scratch_for_stream()
 
         self.custom_ar = None  # parallel.custom_allreduce.CustomAllReduce (set by the engine)
         # TP all-reduces issued from Python: one-shot IPC vs the process group (RCCL / gloo); a call
@@ -575,7 +618,37 @@ class LlamaModel:
         FP8 bytes on the FP8 arm of gemm256, which takes every M."""
         if isinstance(w, Fp8Proj) and w.w is None:
             return ops.gemm_bt(x, w.data, w_exps=w.exps, **kw)
-        return ops.gemm_bt(x, _bf16_copy(w), **kw)
+        return ops.gemm_bt(x, self._bf16_w(w), **kw)
+
+    def mxfp4_scratch_bytes(self) -> int:
+        """Bytes of ONE bf16 image scratch of ``mxfp4_weights_only`` (0 without it): the largest
+        projection.  Every stream that runs the model holds one (``_scratch_for_stream``)."""
+        return 2 * self._mxfp4_scratch_elems
+
+    def _scratch_for_stream(self) -> torch.Tensor:
+        """The current stream's image scratch.  One per stream: two engines sharing this model on two
+        streams each dequantise into their own, and a captured graph keeps the pointer of the stream
+        it was captured on, so a scratch is never freed or moved.  A stream's first use allocates,
+        which a graph capture cannot do: warm the stream up before capturing on it."""
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        buf = self._mxfp4_scratch.get(key)
+        if buf is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("mxfp4_weights_only: this stream has no weight scratch yet and a graph capture "
+                                   "cannot allocate one (run the step once on the stream before capturing)")
+            buf = self._mxfp4_scratch[key] = torch.empty(self._mxfp4_scratch_elems, dtype=torch.bfloat16,
+                                                         device=self.device)
+        return buf
+
+    def _bf16_w(self, w):
+        """The bf16 fragment tensor of a projection: the tensor itself, the resident copy of an
+        ``Fp8Proj`` / ``Mxfp4Proj``, or (``mxfp4_weights_only``: there is none) the image
+        ``ops.weight_dequant_mxfp4`` writes into the current stream's scratch, as an [N, K] view.  The
+        view is valid until the next call on this stream: stream order puts the next dequantiser behind
+        the GEMM that reads it, so a caller takes it right before its GEMM and holds one at a time."""
+        if isinstance(w, Mxfp4Proj) and w.w is None:
+            return ops.weight_dequant_mxfp4(w.data, w.scales, self._scratch_for_stream(), w.group)
+        return _bf16_copy(w)
 
     # FP8 weights: (projection, stream_gemm cfg) pairs that stream the bf16 copy although the cfg has
     # an FP8 instantiation: the per-shape opt-out for ranges that measure slower (profiles/weight_fp8.md)
@@ -594,7 +667,7 @@ class LlamaModel:
             if (self.mxfp4_stream and ops.native().stream_gemm_mxfp4_ok(cfg)
                     and (name, cfg) not in self.MXFP4_STREAM_OFF):
                 return w.data, {"w_scales": w.scales}
-            return w.w, {}
+            return self._bf16_w(w), {}  # (``mxfp4_weights_only``: the scratch image; one at a time)
         if not isinstance(w, Fp8Proj):
             return w, {}
         if self.fp8_stream and ops.native().stream_gemm_fp8_ok(cfg) and (name, cfg) not in self.FP8_STREAM_OFF:
@@ -679,16 +752,20 @@ class LlamaModel:
         c, s = self._stream_choice("qkv", T, L.qkv_w.shape[0], L.qkv_w.shape[1])
         pg = self.proj_group
         R = self.STREAM_CFG_RES16
-        (qw, qe), (ow, oe) = self._stream_w(L.qkv_w, "qkv", c), self._stream_w(L.o_w, "o", R)
+        # (each ``_stream_w`` right before its GEMM: under ``mxfp4_weights_only`` two of them may be
+        # views of the one scratch)
+        qw, qe = self._stream_w(L.qkv_w, "qkv", c)
         qkv = ops.stream_gemm(h, qw, splits=s, cfg=c, nt=True, norm_eps=cfg.eps, w_group=pg.get("qkv", 1), **qe)
         q = kv.write(li, qkv, meta.positions, self.cos_sin, meta.slots, self.hq, self.hkv, D)
         a = kv.decode_attention(li, q, meta.block_tables, meta.ctx_lens, meta.part_size, meta.workspace,
                                 order=meta.order)
+        ow, oe = self._stream_w(L.o_w, "o", R)
         h1 = ops.stream_gemm(a.view(T, self.hq * D), ow, residual=h, cfg=R, nt=True, w_group=pg.get("o", 1), **oe)
         gc, _ = self._stream_choice("gate_up", T, L.gate_up_w.shape[0], L.gate_up_w.shape[1])
-        (gw, ge), (dw, de) = self._stream_w(L.gate_up_w, "gate_up", gc), self._stream_w(L.down_w, "down", R)
+        gw, ge = self._stream_w(L.gate_up_w, "gate_up", gc)
         act = ops.stream_gemm(h1, gw, epilogue=ops.EPI_SWIGLU8, cfg=gc, nt=True, norm_eps=cfg.eps,
                               w_group=pg.get("gate_up", 1), **ge)
+        dw, de = self._stream_w(L.down_w, "down", R)
         return ops.stream_gemm(act, dw, residual=h1, cfg=R, nt=True, w_group=pg.get("down", 1), **de)
 
     # Small decode batches: the paged attention is a chain of dependent memory round trips on a few

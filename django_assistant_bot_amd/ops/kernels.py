@@ -1118,6 +1118,39 @@ def index_dequant_blocks(data_shuf, exps, b0: int, b1: int, out, out_block: int 
     return out
 
 
+def weight_dequant_mxfp4(codes_shuf, scales_shuf, out, group: int = 1, grid_cap: int = 0):
+    """MXFP4 weights -> their bf16 fragment image: ``codes_shuf`` uint8 [N, K/2] in the
+    ``shuffle_weights_mxfp4(..., group)`` layout and ``scales_shuf`` uint8 [N, K/32] in the
+    ``shuffle_scales_mxfp4`` layout -> ``shuffle_weights(weight_dequantize_mxfp4(codes, scales), group)``
+    written to the first N K elements of ``out`` (contiguous bf16 with at least that many; the rest is
+    not touched).  Exact: every dequantised value is a bf16.  Returns the [N, K] view of ``out``.
+    K % 128 == 0, N % (16 group) == 0, 16-byte aligned codes / out, 4-byte aligned scales; ``group`` > 1
+    needs N K 2 < 2^31 bytes (the bound of the grouped layouts).  ``grid_cap`` > 0 bounds the
+    workgroups of the launch (tests: the grid-stride loop at a small shape)."""
+    group, grid_cap = int(group), int(grid_cap)
+    expect(codes_shuf.dtype == torch.uint8 and codes_shuf.dim() == 2 and codes_shuf.is_contiguous(),
+           "codes: contiguous uint8 [N, K/2] (shuffle_weights_mxfp4)")
+    N, K = codes_shuf.shape[0], codes_shuf.shape[1] * 2
+    expect(group >= 1 and grid_cap >= 0, "group >= 1 and grid_cap >= 0")
+    expect(N > 0 and K > 0 and K % 128 == 0 and N % (16 * group) == 0,
+           "weight_dequant_mxfp4 needs K % 128 == 0 and N % (16 group) == 0")
+    expect(group == 1 or N * K * 2 < (1 << 31), "grouped layouts need N K 2 < 2^31 bytes")
+    expect(scales_shuf.dtype == torch.uint8 and scales_shuf.dim() == 2 and scales_shuf.is_contiguous()
+           and tuple(scales_shuf.shape) == (N, K // 32), "scales: contiguous uint8 [N, K/32] (shuffle_scales_mxfp4)")
+    expect(out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() >= N * K,
+           "out: contiguous bf16 with at least N K elements")
+    same_device(codes_shuf, scales_shuf, out)
+    expect(codes_shuf.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 and scales_shuf.data_ptr() % 4 == 0,
+           "codes / out must be 16-byte aligned, scales 4-byte aligned")
+    view = out.view(-1)[:N * K].view(N, K)
+    if not codes_shuf.is_cuda:
+        rows = weight_dequantize_mxfp4(unshuffle_weights_mxfp4(codes_shuf, group), unshuffle_scales_mxfp4(scales_shuf))
+        view.copy_(shuffle_weights(rows, group))
+        return view
+    native().weight_dequant_mxfp4(ptr(codes_shuf), ptr(scales_shuf), ptr(out), N, K, group, grid_cap, stream(out))
+    return view
+
+
 def stream_gemm(x, w, splits=1, epilogue=EPI_NONE, residual=None, out=None, nt=False, cfg=0, norm_eps: float = 0.0,
                 slab_dtype=torch.float32, w_group: int = 1, w_exps=None, w_scales=None):
     """Decode GEMM y = x w^T on the warp-specialised streaming kernel (``stream_gemm.hip``): bf16

@@ -308,6 +308,68 @@ def dequant_mxfp4_sweep(rounds=3, pair_m=192):
         del w4, scratch, resident
 
 
+def mid_mxfp4_sweep(Ms=(192, 384, 640, 1024), rounds=3):
+    """The MXFP4 arm of ``gemm_mid`` on the four Llama-3-8B projection shapes (gate_up: group 8, SwiGLU8) at
+    mid M, cold weights (distinct copies beyond the Infinity Cache, one launch per copy in one HIP graph),
+    the arms alternating round by round:
+    ``bf16``: gemm_mid on resident bf16 copies (the two-copy model); ``deq``: the dequantiser into one
+    scratch + gemm_mid on it (the one-copy model without ``mxfp4_mid``); ``mx``: the MXFP4 arm on the codes
+    (default conversion placement), ``mx1`` / ``mx2``: the conversion after / before the read barrier.
+    ``dispatch_mid``: whether ``ops.gemm_bt`` sends the shape to gemm_mid at all (else gemm256 has it)."""
+    from django_assistant_bot_amd.models.llama import LlamaModel
+
+    shapes = (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336))
+    for name, N, K in shapes:
+        grp = LlamaModel.PROJ_GROUPS.get(name, 1)
+        epi = ops.EPI_SWIGLU8 if name == "gate_up" else ops.EPI_NONE
+        mxb = N * K // 2 + N * K // 32
+        ncopy = max(2, int(6e8 // mxb) + 1)
+        w4, w16 = [], []
+        for _ in range(ncopy):
+            codes = torch.randint(0, 256, (N, K // 2), dtype=torch.uint8, device="cuda")
+            scales = torch.randint(118, 130, (N, K // 32), dtype=torch.uint8, device="cuda")
+            w4.append((codes, scales))  # (any bytes are a valid fragment copy)
+            w16.append(ops.weight_dequant_mxfp4(codes, scales, torch.empty(N * K, dtype=torch.bfloat16, device="cuda"), grp))
+        scratch = torch.empty(N * K, dtype=torch.bfloat16, device="cuda")
+        for M in Ms:
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            out = torch.empty((M, N // 2 if epi == ops.EPI_SWIGLU8 else N), dtype=torch.bfloat16, device="cuda")
+            kw = dict(epilogue=epi, b_group=grp, out=out)
+
+            def deq_calls():
+                calls = []
+                for c, s in w4:
+                    calls.append(lambda c=c, s=s: ops.weight_dequant_mxfp4(c, s, scratch, grp))
+                    calls.append(lambda: ops.gemm_mid(a, scratch.view(N, K), **kw))
+                return calls
+
+            def mx_calls(conv):
+                return [lambda c=c, s=s: ops.gemm_mid(a, c, w_scales=s, convert=conv, **kw) for c, s in w4]
+
+            arms = {"bf16": lambda: graph_time([lambda w=w: ops.gemm_mid(a, w, **kw) for w in w16]),
+                    "deq": lambda: graph_time(deq_calls()) * 2,
+                    "mx": lambda: graph_time(mx_calls(0)),
+                    "mx1": lambda: graph_time(mx_calls(1)),
+                    "mx2": lambda: graph_time(mx_calls(2))}
+            times = {k: [] for k in arms}
+            for _ in range(rounds):
+                for k, fn in arms.items():
+                    times[k].append(fn())
+            assert torch.equal(ops.gemm_mid(a, w4[0][0], w_scales=w4[0][1], epilogue=epi, b_group=grp),
+                               ops.gemm_mid(a, w16[0], epilogue=epi, b_group=grp))
+            res = {"op": f"mid-mxfp4-{name}", "M": M, "N": N, "K": K, "group": grp, "copies": ncopy,
+                   "dispatch_mid": bool(ops.kernels.use_gemm_mid(M, N, K, K))}
+            for k in arms:
+                t = sorted(times[k])[len(times[k]) // 2]
+                res[f"{k}_us"] = round(t * 1e6, 1)
+                res[f"{k}_us_min_max"] = [round(min(times[k]) * 1e6, 1), round(max(times[k]) * 1e6, 1)]
+            for k in ("mx", "mx1", "mx2"):
+                res[f"{k}_vs_bf16"] = round(res[f"{k}_us"] / res["bf16_us"], 3)
+                res[f"{k}_vs_deq"] = round(res[f"{k}_us"] / res["deq_us"], 3)
+            emit(**res)
+        del w4, w16, scratch
+
+
 def attn_suite():
     # prefill: 16 sequences x 1024 tokens, Llama-3-8B heads
     B, T, Hq, Hkv, D, bs = 16, 1024, 32, 8, 128, 64
@@ -582,6 +644,8 @@ if __name__ == "__main__":
         stream_mxfp4_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (1, 16, 64, 128, 256))
     if which == "dequant_mxfp4":
         dequant_mxfp4_sweep()
+    if which == "mid_mxfp4":
+        mid_mxfp4_sweep(tuple(int(m) for m in sys.argv[2].split(",")) if len(sys.argv) > 2 else (192, 384, 640, 1024))
     if which == "decode":
         decode_sweep()
     if which in ("decode", "decodefp8"):

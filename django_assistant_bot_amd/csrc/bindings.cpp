@@ -205,6 +205,16 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("C"), py::arg("ldc"), py::arg("residual"), py::arg("ldr"),
      py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epilogue"), py::arg("slabs"), py::arg("slab_bytes"),
      py::arg("cnt"), py::arg("n_cnt"), py::arg("s"), py::arg("variant") = 0, py::arg("b_group") = 1);
+  m.def("gemm_mid_mxfp4_ok", &dab::gemm_mid_mxfp4_ok);
+  m.def("gemm_mid_mxfp4", [](u A, long lda, u B, u scales, u C, long ldc, u residual, long ldr, int M, int N, int K,
+                             int epilogue, u slabs, long slab_bytes, u cnt, int n_cnt, u s, int b_group, int convert) {
+    check(dab::gemm_mid_mxfp4(CVP(A), lda, CVP(B), CVP(scales), VP(C), ldc, CVP(residual), ldr, M, N, K, epilogue,
+                              VP(slabs), slab_bytes, (int*)cnt, n_cnt, ST(s), b_group, convert),
+          "gemm_mid_mxfp4");
+  }, py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("scales"), py::arg("C"), py::arg("ldc"), py::arg("residual"),
+     py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epilogue"), py::arg("slabs"),
+     py::arg("slab_bytes"), py::arg("cnt"), py::arg("n_cnt"), py::arg("s"), py::arg("b_group") = 1,
+     py::arg("convert") = 0);
   m.def("gemm256_ok", &dab::gemm256_ok);
   m.def("gemm256_stamped", [](u A, long lda, u B, u C, u bias, u residual, int M, int N, int K, int epilogue,
                               int b_shuf, u stamps, int stamp_tiles, u s, int store_aux) {

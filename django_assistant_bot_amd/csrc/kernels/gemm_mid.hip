@@ -30,6 +30,27 @@
 //     grid is at most one workgroup per CU).  Replaces a last-arriver combine (every segment stored
 //     and drained, then an atomic ticket) that cost 5-9 us per launch on the small projections
 //     (profiles/gemm_mid_r6.md).
+//
+// MXFP4-weight arm (template parameter MX, W4A16; profiles/gemm_mid_mxfp4.md): B is the
+// ops.shuffle_weights_mxfp4 copy of the e2m1 codes and S the ops.shuffle_scales_mxfp4 copy of the
+// block scale bytes (the tensors stream_gemm's arm and weight_dequant.hip read).  Everything above
+// stays: K-step 64, the split, the combine, the epilogues.  Only the B side of a stage differs:
+//   * a 128-deep code fragment is 1 KB per 16-row block (lane l: bytes 4c .. 4c + 3 = its operand of
+//     the 32-deep chunk 4j + c).  K-step kk uses the half 8 (kk & 1) .. + 7 of every lane of fragment
+//     kk >> 1, so each stage DMAs the whole fragment of its 16 row blocks (16 KB at the stage's B
+//     offset; wave w blocks w and w + 8, 2 x 16-B instructions) and every fragment is fetched by two
+//     consecutive stages (from L2 the second time);
+//   * the scale dwords of fragment kk >> 1 (one per row: its four chunks' E8M0 bytes) go by ONE 4-B
+//     LDS-DMA per wave to 256 B at B offset + 16 KB + 256 w: lanes 0-15 block w, 16-31 block w + 8,
+//     lanes 32-63 repeat lanes 0-31 (LDS-DMA writes all 64 lanes);
+//   * so kDma = 2 (A) + 2 (codes) + 1 (scales) = 5 VMEM instructions per wave and stage instead of 6;
+//     every counted wait is a multiple of kDma plus the stores in flight (steady state vmcnt(5), + 8 / 16
+//     after an epilogue / a published partial; prologue and tail vmcnt(0 / 5 / 10));
+//   * a lane reads 8 B of codes per row block (ds_read_b64 at lane 16 + 8 (kk & 1)) and its row's scale
+//     dword, and fp4x8_bf16(word, exp_scale(byte)) gives the two bf16x8 operands the bf16 kernel reads
+//     from LDS -- bit for bit the dequantiser's image, hence bit-equal results.  MX = 1 converts after
+//     the read barrier (in front of the MFMA block), MX = 2 before it (beside the other wave group's
+//     MFMAs; the default, kMxConvert).
 #include "common.h"
 #include "launchers.h"
 
@@ -55,6 +76,9 @@ struct GMid {
   int q, r;  // tiles_n * kt = q * gn + r iterations: group j owns q (+1 for j < r)
   unsigned b_bytes, slab_bytes;
   int bgrp;  // row blocks per group of the B copy: 1 (plain) or 8 (shuffle_weights(w, 8))
+  // MXFP4 arm only (B then holds the code bytes): the shuffled scale bytes [N][K / 32]
+  const uint8_t* S;
+  unsigned s_bytes;
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -96,6 +120,10 @@ struct MidGeo {
 constexpr int kE = 8;                  // VMEM stores per wave in every epilogue variant
 constexpr int kSlabSt = 16;            // VMEM stores per wave of a published partial tile
 constexpr int kSlabFloats = 512 * 64;  // one partial tile: 512 threads x 16 f32x4
+// default placement of the MXFP4 conversion: before the read barrier, beside the other wave group's MFMAs
+// (equal to the other placement within noise at M <= 640, 2-3 % faster at M = 1024 and on down at every M:
+// profiles/gemm_mid_mxfp4.md)
+constexpr int kMxConvert = 2;
 
 // group start of the balanced split of the iteration space
 __device__ __forceinline__ int grp_start(int j, int q, int r) { return j * q + min(j, r); }
@@ -108,10 +136,13 @@ __device__ __forceinline__ int grp_owner(int i, int q, int r) {
 
 // BK: K-step width (see MidGeo); DIAG (timing only, benchmarks/gemm_bench.py): 1 = partial tiles
 // are stored and counted but never combined (the output of split tiles is left unwritten)
-template <int EPI, bool RES, int BK, int DIAG = 0>
+// MX: 0 = bf16 weights; MXFP4 codes converted 1 = after / 2 = before the read barrier (BK 64 only)
+template <int EPI, bool RES, int BK, int DIAG = 0, int MX = 0>
 __global__ __launch_bounds__(512) void gemm_mid_kernel(GMid p) {
   using Geo = MidGeo<BK>;
-  constexpr int kStage = Geo::kStage, kStages = Geo::kStages, kDist = Geo::kDist, kDma = Geo::kDma;
+  static_assert(MX == 0 || (BK == 64 && DIAG == 0), "the MXFP4 arm: K-step 64, no DIAG");
+  constexpr int kStage = Geo::kStage, kStages = Geo::kStages, kDist = Geo::kDist;
+  constexpr int kDma = MX ? 5 : Geo::kDma;  // MXFP4: A 2, codes 2, scales 1
   constexpr int kA = Geo::kA;
   __shared__ __attribute__((aligned(16))) char smem[Geo::kSmem];
 
@@ -161,10 +192,28 @@ __global__ __launch_bounds__(512) void gemm_mid_kernel(GMid p) {
   const long a_rows = min(128, p.M - m0);
   const __amdgpu_buffer_rsrc_t rA = mk_rsrc(p.A + (size_t)m0 * p.lda, (unsigned)(((a_rows - 1) * p.lda + p.K) * 2));
   const __amdgpu_buffer_rsrc_t rB = mk_rsrc(p.B, p.b_bytes);
+  // MXFP4: code bytes of one 16-row block over all of K; the fragments of a group adjacent per 128 k
+  const unsigned kq = kblk / 4;
+  const unsigned cq4 = bgrp ? 8192u : 1024u;  // bytes per 128-deep fragment step of a block
+  const unsigned vQ0 = (unsigned)(lane * 16) + (unsigned)w * (bgrp ? 1024u : kq), vQ2 = vQ0 + 8u * kq;
+  // scales [N / 16][K / 128][16][4]: 64 B per (block, fragment), K / 2 bytes per block over all of K
+  const unsigned ke = (unsigned)(p.K / 2);
+  const unsigned vE = (unsigned)(li * 4) + ((unsigned)w + 8u * (unsigned)(gq & 1)) * ke;
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rE = mk_rsrc(p.S, p.s_bytes);
 
   auto stage = [&](int buf, int nt, int kk) {
     char* dst = smem + buf * kStage;
     const unsigned sa = (unsigned)kk * (unsigned)(BK * 2);
+    if constexpr (MX != 0) {
+      const unsigned sq = (unsigned)nt * 16u * kq + (unsigned)(kk >> 1) * cq4;
+      const unsigned se = (unsigned)nt * 16u * ke + (unsigned)(kk >> 1) * 64u;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_void*)(dst + w * 1024), 16, vA0, sa, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_void*)(dst + 8192 + w * 1024), 16, vA1, sa, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_void*)(dst + kA + w * 1024), 16, vQ0, sq, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_void*)(dst + kA + 8192 + w * 1024), 16, vQ2, sq, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rE, (lds_void*)(dst + kA + 16384 + w * 256), 4, vE, se, 0, 0);
+      return;
+    }
     const unsigned sb = (unsigned)nt * 16u * kblk + (unsigned)kk * (unsigned)(BK / 32) * cb;
     if constexpr (BK == 64) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_void*)(dst + w * 1024), 16, vA0, sa, 0, 0);
@@ -193,6 +242,10 @@ __global__ __launch_bounds__(512) void gemm_mid_kernel(GMid p) {
   }
   constexpr int kRowBlk = BK * 32;  // LDS bytes of one 16-row block of A / B in a stage
   const int rdB = kA + wc * 4 * kRowBlk + lane * 16;
+  // MXFP4: row block 4 wc + jn has its 1 KB fragment at B offset + 1 KB (4 wc + jn) and its 16 scale
+  // dwords at B offset + 16 KB + 256 ((4 wc + jn) & 7) + 64 ((4 wc + jn) >> 3)
+  const int rdQ = kA + wc * 4096 + lane * 16;
+  const int rdE = kA + 16384 + (wc & 1) * 1024 + (wc >> 1) * 64 + li * 4;
 
   bf16x8 af[4][KS];
   bf16x8 bfr[4][KS];
@@ -255,11 +308,29 @@ __global__ __launch_bounds__(512) void gemm_mid_kernel(GMid p) {
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) af[i][ks] = *reinterpret_cast<const bf16x8*>(sb + i * 16 * (BK * 2) + rdA[ks]);
+      [[maybe_unused]] u32x2 qw[4];   // MXFP4: the lane's codes of this K-step's two chunks
+      [[maybe_unused]] uint32_t qe[4];  // and its row's two scale bytes (low 16 bits)
+      [[maybe_unused]] auto convert = [&]() {
 #pragma unroll
-      for (int jn = 0; jn < 4; ++jn)
+        for (int jn = 0; jn < 4; ++jn) {
+          bfr[jn][0] = fp4x8_bf16(qw[jn][0], exp_scale(qe[jn] & 0xff));
+          bfr[jn][KS - 1] = fp4x8_bf16(qw[jn][1], exp_scale((qe[jn] >> 8) & 0xff));
+        }
+      };
+      if constexpr (MX != 0) {
+        const int h = kk & 1;  // which half of the 128-deep fragment
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-          bfr[jn][ks] = *reinterpret_cast<const bf16x8*>(sb + rdB + jn * kRowBlk + ks * 1024);
+        for (int jn = 0; jn < 4; ++jn) {
+          qw[jn] = *reinterpret_cast<const u32x2*>(sb + rdQ + jn * 1024 + 8 * h);
+          qe[jn] = *reinterpret_cast<const uint32_t*>(sb + rdE + jn * 256) >> (16 * h);
+        }
+      } else {
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn)
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks)
+            bfr[jn][ks] = *reinterpret_cast<const bf16x8*>(sb + rdB + jn * kRowBlk + ks * 1024);
+      }
       // the stage kDist ahead goes into the buffer read one phase ago
       if (s_it < end) {
         stage(b == 0 ? kStages - 1 : b - 1, s_nt, s_kk);
@@ -277,8 +348,20 @@ __global__ __launch_bounds__(512) void gemm_mid_kernel(GMid p) {
         else wait_vmc<0>();
       }
       after_st = 0;
+      if constexpr (MX == 2) {  // converted before the barrier: pinned there by the empty asm
+        convert();
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn)
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(bfr[jn][ks]));
+      }
       mread_bar();
       if (pend_flag >= 0 && ++pend_phases >= 2) raise_flag();  // this phase's wait retired the stores
+      if constexpr (MX == 1) {  // converted after the barrier, among the MFMAs
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn) asm volatile("" : "+v"(qw[jn]), "+v"(qe[jn]));
+        convert();
+      }
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
@@ -487,9 +570,11 @@ int gemm_mid_counters(int M, int N) {
 // (BK 64), 32 / 64 force the K-step, + 1000 = DIAG 1 (split tiles not combined: timing only).
 // BK 32 (6-stage ring) measured 5-20 % slower than BK 64 on every mid shape, with LDS bank
 // conflicts on its 64-B A rows (profiles/gemm_mid_r6.md): kept as an A/B arm only.
-int gemm_mid(const void* A, long lda, const void* B, void* C, long ldc, const void* residual, long ldr, int M, int N,
-             int K, int epilogue, void* slabs, long slab_bytes, int* cnt, int n_cnt, hipStream_t s, int variant,
-             int b_group) {
+namespace {
+// the one launch path: scales == nullptr is the bf16 kernel, otherwise its MXFP4 arm (mx 1 / 2)
+int mid_launch(const void* A, long lda, const void* B, const void* scales, int mx, void* C, long ldc,
+               const void* residual, long ldr, int M, int N, int K, int epilogue, void* slabs, long slab_bytes, int* cnt,
+               int n_cnt, hipStream_t s, int variant, int b_group) {
   if (!gemm_mid_ok(M, N, K, lda)) return hipErrorInvalidValue;
   if (b_group != 1 && b_group != 8) return hipErrorInvalidValue;
   if (epilogue != MID_NONE && epilogue != MID_SWIGLU8) return hipErrorInvalidValue;
@@ -525,6 +610,7 @@ int gemm_mid(const void* A, long lda, const void* B, void* C, long ldc, const vo
   p.b_bytes = (unsigned)((long)N * K * 2);
   p.slab_bytes = (unsigned)slab_bytes;
   p.bgrp = b_group;
+  p.S = (const uint8_t*)scales;
 #define MID_LAUNCH(E, R, BKV, D) hipLaunchKernelGGL((gemm_mid_kernel<E, R, BKV, D>), dim3(grid), dim3(512), 0, s, p)
 #define MID_BK(E, R)                       \
   do {                                     \
@@ -537,12 +623,51 @@ int gemm_mid(const void* A, long lda, const void* B, void* C, long ldc, const vo
       MID_LAUNCH(E, R, 32, 0);             \
     }                                      \
   } while (0)
-  if (epilogue == MID_SWIGLU8) MID_BK(MID_SWIGLU8, false);
+#define MID_MX(E, R)                                                                                    \
+  do {                                                                                                  \
+    if (mx == 2) hipLaunchKernelGGL((gemm_mid_kernel<E, R, 64, 0, 2>), dim3(grid), dim3(512), 0, s, p); \
+    else hipLaunchKernelGGL((gemm_mid_kernel<E, R, 64, 0, 1>), dim3(grid), dim3(512), 0, s, p);         \
+  } while (0)
+  if (scales) {
+    p.b_bytes = (unsigned)((long)N * K / 2);
+    p.s_bytes = (unsigned)((long)N * K / 32);
+    if (epilogue == MID_SWIGLU8) MID_MX(MID_SWIGLU8, false);
+    else if (residual) MID_MX(MID_NONE, true);
+    else MID_MX(MID_NONE, false);
+  } else if (epilogue == MID_SWIGLU8) MID_BK(MID_SWIGLU8, false);
   else if (residual) MID_BK(MID_NONE, true);
   else MID_BK(MID_NONE, false);
+#undef MID_MX
 #undef MID_BK
 #undef MID_LAUNCH
   return hipGetLastError();
+}
+}  // namespace
+
+int gemm_mid(const void* A, long lda, const void* B, void* C, long ldc, const void* residual, long ldr, int M, int N,
+             int K, int epilogue, void* slabs, long slab_bytes, int* cnt, int n_cnt, hipStream_t s, int variant,
+             int b_group) {
+  return mid_launch(A, lda, B, nullptr, 0, C, ldc, residual, ldr, M, N, K, epilogue, slabs, slab_bytes, cnt, n_cnt, s,
+                    variant, b_group);
+}
+
+// The MXFP4 arm's shapes: gemm_mid's, with whole 128-deep code fragments (the code bytes N K / 2 then
+// fit 32-bit offsets because the bf16 bytes N K 2 do).
+int gemm_mid_mxfp4_ok(int M, int N, int K, long lda) {
+  return gemm_mid_ok(M, N, K, lda) && K % 128 == 0 && (long)N * K / 2 < (1L << 32);
+}
+
+// B: ops.shuffle_weights_mxfp4(codes, b_group) [N][K / 2] (16-B aligned), scales: ops.shuffle_scales_mxfp4
+// [N][K / 32] (4-B aligned); everything else as gemm_mid, whose result on the dequantised weights this
+// equals bit for bit.  convert (A/B): 0 default, 1 = after / 2 = before the read barrier.
+int gemm_mid_mxfp4(const void* A, long lda, const void* B, const void* scales, void* C, long ldc, const void* residual,
+                   long ldr, int M, int N, int K, int epilogue, void* slabs, long slab_bytes, int* cnt, int n_cnt,
+                   hipStream_t s, int b_group, int convert) {
+  if (!gemm_mid_mxfp4_ok(M, N, K, lda)) return hipErrorInvalidValue;
+  if (!A || !B || !scales || !C || (uintptr_t)B % 16 || (uintptr_t)scales % 4) return hipErrorInvalidValue;
+  if (convert < 0 || convert > 2) return hipErrorInvalidValue;
+  return mid_launch(A, lda, B, scales, convert == 0 ? kMxConvert : convert, C, ldc, residual, ldr, M, N, K, epilogue,
+                    slabs, slab_bytes, cnt, n_cnt, s, 0, b_group);
 }
 
 }  // namespace dab

@@ -117,6 +117,15 @@ int gemm_mid_counters(int M, int N);
 int gemm_mid(const void* A, long lda, const void* B, void* C, long ldc, const void* residual, long ldr, int M, int N,
              int K, int epilogue, void* slabs, long slab_bytes, int* cnt, int n_cnt, hipStream_t s, int variant = 0,
              int b_group = 1);
+// The MXFP4-weight arm of the same kernel (W4A16): B = ops.shuffle_weights_mxfp4(codes, b_group) [N][K / 2],
+// scales = ops.shuffle_scales_mxfp4 [N][K / 32]; bit for bit gemm_mid on the dequantised weights.
+// Eligible: gemm_mid_ok and K % 128 == 0, 16-B aligned codes, 4-B aligned scales, 32-bit code offsets;
+// anything else -> hipErrorInvalidValue, nothing launched.  convert (A/B harness): where the codes
+// become bf16, 0 = default, 1 = after / 2 = before the phase's read barrier.
+int gemm_mid_mxfp4_ok(int M, int N, int K, long lda);
+int gemm_mid_mxfp4(const void* A, long lda, const void* B, const void* scales, void* C, long ldc, const void* residual,
+                   long ldr, int M, int N, int K, int epilogue, void* slabs, long slab_bytes, int* cnt, int n_cnt,
+                   hipStream_t s, int b_group = 1, int convert = 0);
 
 // stream_gemm.hip (warp-specialised decode GEMM, M <= 256: bf16 / SwiGLU / fp32 split-K slabs; cfg selects
 // the tile / ring configuration, stream_gemm_bn(cfg) = weight rows per workgroup)

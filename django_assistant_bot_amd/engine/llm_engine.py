@@ -114,7 +114,7 @@ class LLMEngine:
                  pipeline_decode: bool = True, shared_model: LlamaModel | None = None,
                  kv_cache_dtype: str | None = None, kv_scratch_blocks: int | None = None,
                  weight_dtype: str | None = None, fp8_weights_only: bool | None = None,
-                 mxfp4_weights_only: bool | None = None):
+                 mxfp4_weights_only: bool | None = None, mxfp4_mid: bool | None = None):
         """``shared_model``: serve with another engine's ``LlamaModel`` (one copy of the weights, a
         KV pool / scheduler / HIP graphs of this engine's own; e.g. two engines on two streams whose
         prefill and decode phases overlap: bench.py --mode overlap).
@@ -143,7 +143,13 @@ class LLMEngine:
         (``LlamaModel(mxfp4_weights_only=True)``: 4.25 / 16 of the bf16 projection memory plus one scratch
         per stream, ``stats["weight_scratch_bytes"]``; bit-identical to the two-copy MXFP4 model); ``None``
         reads ``DAB_WEIGHT_MXFP4_ONLY`` from the environment, else off.  The same refusals as the model's;
-        with ``shared_model`` the engine adopts the model's."""
+        with ``shared_model`` the engine adopts the model's.
+
+        ``mxfp4_mid`` (opt-in on top of ``weight_dtype="mxfp4"``, TP 1; with or without
+        ``mxfp4_weights_only``): the model's gemm_mid calls read the MXFP4 codes on that kernel's MXFP4 arm
+        (``LlamaModel(mxfp4_mid=True)``; the same tokens; ``stats["weight_mid_mxfp4"]``); ``None`` reads
+        ``DAB_WEIGHT_MXFP4_MID`` from the environment, else off.  With ``shared_model`` the engine adopts
+        the model's."""
         self.cfg = decoder_config(model) if isinstance(model, str) else model
         cfg = self.cfg
         if shared_model is not None:
@@ -160,6 +166,10 @@ class LLMEngine:
                 raise ValueError(f"mxfp4_weights_only={mxfp4_weights_only!r} conflicts with the shared model's "
                                  f"{have_only!r}")
             mxfp4_weights_only = have_only
+            have_mid = bool(getattr(shared_model, "mxfp4_mid", False))
+            if mxfp4_mid is not None and bool(mxfp4_mid) != have_mid:
+                raise ValueError(f"mxfp4_mid={mxfp4_mid!r} conflicts with the shared model's {have_mid!r}")
+            mxfp4_mid = have_mid
         elif weight_dtype is None:
             weight_dtype = os.environ.get("DAB_WEIGHT_DTYPE") or "bf16"
         if fp8_weights_only is None:
@@ -168,6 +178,9 @@ class LLMEngine:
         if mxfp4_weights_only is None:
             mxfp4_weights_only = parse_flag(os.environ.get("DAB_WEIGHT_MXFP4_ONLY"))
         mxfp4_weights_only = bool(mxfp4_weights_only)
+        if mxfp4_mid is None:
+            mxfp4_mid = parse_flag(os.environ.get("DAB_WEIGHT_MXFP4_MID"))
+        mxfp4_mid = bool(mxfp4_mid)
         if weight_dtype not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
         if weight_dtype != "bf16" and tp_size > 1:
@@ -180,9 +193,12 @@ class LLMEngine:
             raise ValueError("mxfp4_weights_only and fp8_weights_only are mutually exclusive")
         if mxfp4_weights_only and weight_dtype != "mxfp4":
             raise ValueError("mxfp4_weights_only needs weight_dtype='mxfp4'")
+        if mxfp4_mid and weight_dtype != "mxfp4":
+            raise ValueError("mxfp4_mid needs weight_dtype='mxfp4'")
         self.weight_dtype = weight_dtype
         self.fp8_weights_only = fp8_weights_only
         self.mxfp4_weights_only = mxfp4_weights_only
+        self.mxfp4_mid = mxfp4_mid
         if kv_cache_dtype is None:
             kv_cache_dtype = os.environ.get("DAB_KV_CACHE_DTYPE") or "bf16"
         if kv_cache_dtype not in ("bf16", "fp8"):
@@ -217,7 +233,7 @@ class LLMEngine:
             self.model = LlamaModel(cfg, weights, self.device, tp_group=tp_group, tp_size=tp_size,
                                     interleaved_mlp=interleaved_mlp, consume=own_weights, tp_rank=tp_rank,
                                     weight_dtype=weight_dtype, fp8_weights_only=fp8_weights_only,
-                                    mxfp4_weights_only=mxfp4_weights_only)
+                                    mxfp4_weights_only=mxfp4_weights_only, mxfp4_mid=mxfp4_mid)
         del weights
         if self.is_gpu and shared_model is None:
             # the caller's weight dict held the row-major originals while the model converted them
@@ -286,7 +302,9 @@ class LLMEngine:
                       # tensors, and one bf16 image scratch of ``mxfp4_weights_only`` (0 without it)
                       "weight_bf16_copy": not (fp8_weights_only or mxfp4_weights_only),
                       "weight_bytes": self.model.projection_bytes(),
-                      "weight_scratch_bytes": self.model.mxfp4_scratch_bytes()}
+                      "weight_scratch_bytes": self.model.mxfp4_scratch_bytes(),
+                      # ``mxfp4_mid``: gemm_mid calls read the MXFP4 codes (its MXFP4 arm)
+                      "weight_mid_mxfp4": mxfp4_mid}
         # decode static buffers (graph inputs / outputs)
         self.use_graphs = use_graphs and self.is_gpu
         dev = self.device

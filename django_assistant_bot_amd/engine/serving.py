@@ -231,8 +231,9 @@ def get_llm_worker(model: str, **engine_kwargs) -> LLMWorker:
             engine_kwargs.setdefault("max_prefill_tokens", setting("MAX_BATCH_TOKENS", 65536))
             engine_kwargs.setdefault("kv_cache_dtype", setting("KV_CACHE_DTYPE", None))  # None: env, else bf16
             engine_kwargs.setdefault("weight_dtype", setting("WEIGHT_DTYPE", None))  # (likewise)
-            # None: DAB_WEIGHT_FP8_ONLY / DAB_WEIGHT_MXFP4_ONLY, else off
-            for kw, name in (("fp8_weights_only", "WEIGHT_FP8_ONLY"), ("mxfp4_weights_only", "WEIGHT_MXFP4_ONLY")):
+            # None: DAB_WEIGHT_FP8_ONLY / DAB_WEIGHT_MXFP4_ONLY / DAB_WEIGHT_MXFP4_MID, else off
+            for kw, name in (("fp8_weights_only", "WEIGHT_FP8_ONLY"), ("mxfp4_weights_only", "WEIGHT_MXFP4_ONLY"),
+                             ("mxfp4_mid", "WEIGHT_MXFP4_MID")):
                 if kw not in engine_kwargs:
                     from .llm_engine import parse_flag
 

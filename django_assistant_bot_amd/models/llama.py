@@ -250,7 +250,8 @@ class LlamaModel:
     def __init__(self, cfg: DecoderConfig, weights: dict, device, tp_group=None, tp_size: int = 1,
                  interleaved_mlp: bool = False, fragment_layout: bool = True, consume: bool = False,
                  tp_rank: int | None = None, vocab_parallel: bool = True, small_norm_fused: bool | None = None,
-                 weight_dtype: str = "bf16", fp8_weights_only: bool = False, mxfp4_weights_only: bool = False):
+                 weight_dtype: str = "bf16", fp8_weights_only: bool = False, mxfp4_weights_only: bool = False,
+                 mxfp4_mid: bool = False):
         """``weight_dtype="fp8"`` (opt-in, TP 1): the qkv / o / gate_up / down weights are quantised at
         load time to e4m3fn bytes with one power-of-two exponent per output row
         (``ops.weight_quantize_fp8``) and the model computes with the dequantised values everywhere.
@@ -287,6 +288,13 @@ class LlamaModel:
         model's.  Every projection must become an ``Mxfp4Proj`` on the GPU (K % 128 == 0, fragment
         layout; ValueError otherwise).  On the CPU it changes nothing.
 
+        ``mxfp4_mid`` (opt-in on top of ``weight_dtype="mxfp4"``, TP 1, fragment layout; with or without
+        ``mxfp4_weights_only``): an ``Mxfp4Proj`` call that would take ``gemm_mid`` (``ops.kernels.use_gemm_mid``)
+        runs that kernel's MXFP4 arm on the codes and scales (``ops.gemm_bt(..., w_scales=)``) instead of
+        its bf16 copy, or, in the one-copy mode, instead of the dequantiser and the scratch image.  Bit for
+        bit the same result; projections named in ``MXFP4_MID_OFF`` and every other call keep today's
+        path.  On the CPU it changes nothing.
+
         ``consume``: the entries of ``weights`` are popped as the model takes them over, so each
         original is freed as soon as its fragment-layout copy exists (peak HBM = model + one
         tensor: 70B at TP 1 needs it, 2 x 140 GB would not fit in 288 GB).
@@ -318,6 +326,12 @@ class LlamaModel:
                 raise ValueError("mxfp4_weights_only needs weight_dtype='mxfp4'")
             if not fragment_layout:
                 raise ValueError("mxfp4_weights_only needs the fragment layout (fragment_layout=True)")
+        self.mxfp4_mid = bool(mxfp4_mid)
+        if self.mxfp4_mid:
+            if weight_dtype != "mxfp4":
+                raise ValueError("mxfp4_mid needs weight_dtype='mxfp4'")
+            if not fragment_layout:
+                raise ValueError("mxfp4_mid needs the fragment layout (fragment_layout=True)")
         self.cfg = cfg
         self.device = torch.device(device)
         if tp_rank is None:
@@ -611,13 +625,23 @@ class LlamaModel:
                 sd = torch.bfloat16 if (self.slab_bf16 and self.tp_size == 1 and not slab_f32) else torch.float32
                 out = ops.stream_gemm(x, sw, splits=s, cfg=cfg, nt=True, slab_dtype=sd, w_group=grp, **e)
                 return ops.slab_reduce(out) if (s > 1 and not allow_slabs) else out
-        return self._mfma(x, w, epilogue=epilogue, shuffled=self.frag, b_group=grp)
+        return self._mfma(x, w, name=name, epilogue=epilogue, shuffled=self.frag, b_group=grp)
 
-    def _mfma(self, x, w, **kw):
+    # ``mxfp4_mid``: projections that keep the bf16 path although their call would take gemm_mid's
+    # MXFP4 arm: the opt-out for projections that measure slower (profiles/gemm_mid_mxfp4.md)
+    MXFP4_MID_OFF: frozenset = frozenset()
+
+    def _mfma(self, x, w, name: str = "", **kw):
         """``ops.gemm_bt`` on a projection: its bf16 copy, or (``fp8_weights_only``: there is none) the
-        FP8 bytes on the FP8 arm of gemm256, which takes every M."""
+        FP8 bytes on the FP8 arm of gemm256, which takes every M.  ``mxfp4_mid``: the codes of an
+        ``Mxfp4Proj`` on gemm_mid's MXFP4 arm wherever the bf16 call would take gemm_mid."""
         if isinstance(w, Fp8Proj) and w.w is None:
             return ops.gemm_bt(x, w.data, w_exps=w.exps, **kw)
+        if (self.mxfp4_mid and isinstance(w, Mxfp4Proj) and x.is_cuda and name not in self.MXFP4_MID_OFF
+                and kw.get("rows") is None and kw.get("as_m") is None):
+            (M, K), N, lda = x.shape, w.shape[0], x.stride(0)
+            if ops.kernels.use_gemm_mid(M, N, K, lda) and ops.kernels.gemm_mid_mxfp4_ok(M, N, K, lda):
+                return ops.gemm_bt(x, w.data, w_scales=w.scales, **kw)
         return ops.gemm_bt(x, self._bf16_w(w), **kw)
 
     def mxfp4_scratch_bytes(self) -> int:
@@ -867,18 +891,19 @@ class LlamaModel:
         if rows.dtype != torch.int32:
             rows = rows.to(torch.int32)
         pg = self.proj_group
-        res = self._mfma(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=True,
+        res = self._mfma(a.view(T, self.hq * D), L.o_w, name="o", residual=residual, shuffled=True,
                          b_group=pg.get("o", 1), rows=rows)
         h, _ = ops.rmsnorm(res, L.mlp_norm, self.cfg.eps)
-        act = self._mfma(h, L.gate_up_w, epilogue=ops.EPI_SWIGLU8, shuffled=True,
+        act = self._mfma(h, L.gate_up_w, name="gate_up", epilogue=ops.EPI_SWIGLU8, shuffled=True,
                          b_group=pg.get("gate_up", 1), as_m=T)
-        return None, self._mfma(act, L.down_w, residual=res, shuffled=True, b_group=pg.get("down", 1), as_m=T)
+        return None, self._mfma(act, L.down_w, name="down", residual=res, shuffled=True, b_group=pg.get("down", 1),
+                                as_m=T)
 
     def _layer_tail(self, L, a, residual, sk, fuse, slabs_ok, T, D):
         """o projection, MLP norm, gate_up (+SwiGLU), down: -> (next layer input, residual stream)."""
         cfg = self.cfg
         if fuse:
-            residual = self._mfma(a.view(T, self.hq * D), L.o_w, residual=residual, shuffled=self.frag,
+            residual = self._mfma(a.view(T, self.hq * D), L.o_w, name="o", residual=residual, shuffled=self.frag,
                                   b_group=self.proj_group.get("o", 1))
             h, _ = ops.rmsnorm(residual, L.mlp_norm, cfg.eps)
         elif sk and self.tp_size > 1:
@@ -894,7 +919,7 @@ class LlamaModel:
         if h.is_cuda and epi == ops.EPI_NONE:
             act = ops.silu_mul(act)
         if fuse:
-            return None, self._mfma(act, L.down_w, residual=residual, shuffled=self.frag,
+            return None, self._mfma(act, L.down_w, name="down", residual=residual, shuffled=self.frag,
                                     b_group=self.proj_group.get("down", 1))
         if sk and self.tp_size > 1:  # reduced inside the next layer's (or the final) norm launch
             return self._tp_partial(self._proj(act, L.down_w, sk, True, name="down"), cfg.hidden), residual

@@ -584,7 +584,8 @@ def use_gemm256(M: int, N: int, K: int, lda: int, ldb: int) -> bool:
 
 
 def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, row_group=None, q_group=None,
-            allow=None, out=None, shuffled=False, n=None, b_group: int = 1, rows=None, as_m=None, w_exps=None):
+            allow=None, out=None, shuffled=False, n=None, b_group: int = 1, rows=None, as_m=None, w_exps=None,
+            w_scales=None):
     """C = A . B^T (+bias) (+act) (+residual) on MFMA; A [M, K], B [N, K] (K-contiguous rows).
 
     ``shuffled``: B is a ``shuffle_weights`` copy (the layout the decode GEMM streams, so a model
@@ -603,8 +604,30 @@ def gemm_bt(A, B, bias=None, residual=None, epilogue=EPI_NONE, out_f32=False, ro
     the e4m3fn bytes (``shuffled=True`` required) and ``w_exps`` [N] the rows' exponent bytes.  Every
     such call, at any M and with ``rows`` / ``as_m``, runs the FP8 arm of gemm256 (no other kernel
     reads the bytes): plain / residual / SwiGLU8 projections with N % 256 == 0 and K % 128 == 0,
-    anything else is refused.  Bit for bit ``gemm256`` on the dequantised weights."""
+    anything else is refused.  Bit for bit ``gemm256`` on the dequantised weights.
+
+    ``w_scales`` (MXFP4 weights, W4A16; not together with ``w_exps``): B is the uint8
+    ``shuffle_weights_mxfp4(codes, b_group)`` copy [N, K/2] (``shuffled=True`` required) and ``w_scales``
+    the ``shuffle_scales_mxfp4`` copy [N, K/32].  Plain / residual / SwiGLU8 projections without bias,
+    filters, ``rows`` or ``as_m``, and only where the bf16 call would take ``gemm_mid``
+    (``use_gemm_mid``) and ``gemm_mid_mxfp4_ok`` holds: the MXFP4 arm of that kernel, bit for bit its
+    result on the dequantised weights.  Any other shape is refused (no other kernel reads the codes).
+    On the CPU B and ``w_scales`` are row-major."""
     expect(b_group == 1 or (shuffled and b_group == 8), "b_group: 1, or 8 with a shuffled copy")
+    if w_scales is not None:
+        expect(w_exps is None, "w_exps (FP8 weights) and w_scales (MXFP4 weights) are mutually exclusive")
+        expect(shuffled, "MXFP4 weights (w_scales): B must be the shuffle_weights_mxfp4 copy (shuffled=True)")
+        expect(bias is None and epilogue in (EPI_NONE, EPI_SWIGLU8) and not out_f32 and row_group is None
+               and q_group is None and allow is None and n is None and rows is None and as_m is None,
+               "MXFP4 weights (w_scales): plain / residual / SwiGLU8 projections only, no rows / as_m (the gemm_mid "
+               "MXFP4 arm)")
+        if A.is_cuda:
+            expect(A.dim() == 2 and B.dim() == 2, "MXFP4 weights (w_scales): A [M, K], B [N, K/2]")
+            (M, K), N = A.shape, B.shape[0]
+            expect(use_gemm_mid(M, N, K, A.stride(0)) and gemm_mid_mxfp4_ok(M, N, K, A.stride(0)),
+                   "MXFP4 weights (w_scales): the shape does not take gemm_mid's MXFP4 arm, and no other kernel reads "
+                   "the codes")
+        return gemm_mid(A, B, residual=residual, epilogue=epilogue, out=out, b_group=b_group, w_scales=w_scales)
     if w_exps is not None:
         expect(shuffled, "FP8 weights (w_exps): B must be the shuffle_weights_fp8 copy (shuffled=True)")
         expect(bias is None and epilogue in (EPI_NONE, EPI_SWIGLU8) and not out_f32 and row_group is None
@@ -813,17 +836,52 @@ def gemm_mid_ok(M: int, N: int, K: int, lda: int) -> bool:
     return bool(native().gemm_mid_ok(M, N, K, lda)) and -(-M // 128) * (N // 256) <= (1 << 16)
 
 
-def gemm_mid(A, B, residual=None, epilogue=EPI_NONE, out=None, variant: int = 0, b_group: int = 1):
+def gemm_mid_mxfp4_ok(M: int, N: int, K: int, lda: int) -> bool:
+    """Shapes the MXFP4 arm of ``gemm_mid`` serves: ``gemm_mid_ok`` and K % 128 == 0."""
+    return gemm_mid_ok(M, N, K, lda) and bool(native().gemm_mid_mxfp4_ok(M, N, K, lda))
+
+
+def gemm_mid(A, B, residual=None, epilogue=EPI_NONE, out=None, variant: int = 0, b_group: int = 1, w_scales=None,
+             convert: int = 0):
     """C = A . B^T (+ residual) or SwiGLU over 8-row [gate | up] groups, B a ``shuffle_weights`` copy:
     the mid-M kernel (``gemm_mid.hip``: grouped stream-K, 128 x 256 tiles, in-launch owner combine) for
     M = 256..4096 (mixed serving steps, single prompts).  Bit-reproducible: the split-K partials are
     summed in a fixed order.  ``variant`` (A/B harness): 32 / 64 force the K-step; + 1000 leaves
-    split tiles uncombined (timing only)."""
+    split tiles uncombined (timing only).
+
+    ``w_scales`` (MXFP4 weights, W4A16): ``B`` is the uint8 ``shuffle_weights_mxfp4(codes, b_group)`` copy
+    [N, K/2] and ``w_scales`` the ``shuffle_scales_mxfp4`` copy [N, K/32]; the kernel's MXFP4 arm converts
+    the codes in registers and gives, bit for bit, what the bf16 kernel gives on
+    ``shuffle_weights(weight_dequantize_mxfp4(...), b_group)``.  K % 128 == 0, ``variant`` 0 only;
+    ``convert`` (A/B harness): 1 / 2 place the conversion after / before the phase's read barrier.  On
+    the CPU both are row-major and the result is ``ref.gemm_bt`` on the dequantised rows."""
+    fp4 = w_scales is not None
+    expect(epilogue in (EPI_NONE, EPI_SWIGLU8), "gemm_mid epilogues: none (+residual) or SwiGLU8")
+    expect(not fp4 or int(variant) == 0, "gemm_mid MXFP4 arm: variant 0 only")
+    expect(fp4 or int(convert) == 0, "convert: the MXFP4 arm only")
+    if fp4 and not A.is_cuda:
+        expect(epilogue == EPI_NONE or residual is None, "swiglu8 epilogue takes no residual")
+        y = ref.gemm_bt(A, weight_dequantize_mxfp4(B, w_scales).to(A.dtype), None, residual, epilogue)
+        return y if out is None else out.copy_(y)
+    expect(A.dim() == 2 and B.dim() == 2, "A [M, K], B [N, K] (MXFP4: [N, K/2])")
     M, K = A.shape
     N = B.shape[0]
-    expect(A.is_cuda and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16, "bf16 CUDA operands required")
-    expect(A.stride(-1) == 1 and B.is_contiguous() and B.shape[1] == K, "A K-contiguous, B a contiguous [N, K] copy")
-    expect(epilogue in (EPI_NONE, EPI_SWIGLU8), "gemm_mid epilogues: none (+residual) or SwiGLU8")
+    if fp4:
+        expect(A.is_cuda and A.dtype == torch.bfloat16 and B.is_cuda and B.dtype == torch.uint8 and B.is_contiguous()
+               and B.data_ptr() % 16 == 0,
+               "MXFP4 weights: bf16 CUDA A, contiguous 16-byte aligned uint8 fragment copy [N, K/2]")
+        expect(A.stride(-1) == 1 and K % 128 == 0 and B.shape[1] * 2 == K,
+               "MXFP4 weights: A K-contiguous, K % 128 == 0, B [N, K/2]")
+        expect(w_scales.dtype == torch.uint8 and w_scales.is_cuda and w_scales.dim() == 2
+               and tuple(w_scales.shape) == (N, K // 32) and w_scales.is_contiguous() and w_scales.data_ptr() % 4 == 0,
+               "w_scales must be the uint8 [N, K/32] shuffle_scales_mxfp4 copy (contiguous, 4-byte aligned)")
+        same_device(A, B, w_scales, residual, out)
+        expect(gemm_mid_mxfp4_ok(M, N, K, A.stride(0)), "gemm_mid MXFP4 arm: N % 256, K % 128, M <= 4096, 16-B rows")
+        expect(int(convert) in (0, 1, 2), "convert: 0, 1 or 2")
+    else:
+        expect(A.is_cuda and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16, "bf16 CUDA operands required")
+        expect(A.stride(-1) == 1 and B.is_contiguous() and B.shape[1] == K,
+               "A K-contiguous, B a contiguous [N, K] copy")
     expect(gemm_mid_ok(M, N, K, A.stride(0)), "gemm_mid: N % 256, K % 64, M <= 4096, 16-B rows")
     expect(b_group in (1, 8), "gemm_mid: b_group 1 or 8")
     n_out = N // 2 if epilogue == EPI_SWIGLU8 else N
@@ -835,6 +893,11 @@ def gemm_mid(A, B, residual=None, epilogue=EPI_NONE, out=None, variant: int = 0,
     expect(out.dtype == torch.bfloat16 and out.stride(-1) == 1 and tuple(out.shape) == (M, n_out), "bad output")
     s = stream(A)
     slabs, cnt = _mid_workspace(A.device, s)
+    if fp4:
+        native().gemm_mid_mxfp4(ptr(A), A.stride(0), ptr(B), ptr(w_scales), ptr(out), out.stride(0), ptr(residual),
+                                residual.stride(0) if residual is not None else 0, M, N, K, int(epilogue), ptr(slabs),
+                                slabs.numel() * 4, ptr(cnt), cnt.numel(), s, int(b_group), int(convert))
+        return out
     native().gemm_mid(ptr(A), A.stride(0), ptr(B), ptr(out), out.stride(0), ptr(residual),
                       residual.stride(0) if residual is not None else 0, M, N, K, int(epilogue), ptr(slabs),
                       slabs.numel() * 4, ptr(cnt), cnt.numel(), s, int(variant), int(b_group))
